@@ -24,7 +24,11 @@ default) ahead of that run's process_device_steps call, not one per block
 (`--per-call`: one broadcast and one call per step).
 
 Prints ONE JSON line on rank 0 (driver contract), with `roofline` for the fused
-kernel and `cpu_baseline` from the oracle port on this host (rank 0, N=1).
+kernel.  A plain run sets up, warms up, times the steps, writes the last
+step's output with `--dump-outputs DIR` and prints that line: its `roofline`
+comes from the HIP events around the timed steps, and `cpu_baseline` and
+`roofline.traffic` are null.  Everything below needs `--full`:
+`cpu_baseline` is the oracle port timed on this host (rank 0, N=1);
 `roofline.launch_us` is the kernel's average duration from a rocprofv3
 --kernel-trace --stats child pass of this same command (run before this
 process touches the GPU; `--kt-out DIR` keeps its csv files, profiles/r6/
@@ -106,6 +110,12 @@ def parse():
     p.add_argument("--ir", type=int, default=48000)
     p.add_argument("--dry", choices=["per-channel", "shared"], default="per-channel")
     p.add_argument("--ring", type=int, default=32, help="distinct input/output blocks kept in HBM")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the cpu_baseline legs and the rocprofv3 "
+                        "child passes (--pmc, --kt); without it --no-cpu-baseline, --pmc off and --kt off are implied")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the last timed step's output block as DIR/y.npy "
+                        "(f32 [channels][block]; DIR/y.rank<r>.npy per rank when N>1)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=8.0, help="target CPU time per baseline leg")
     p.add_argument("--pmc", choices=["auto", "off"], default="auto",
@@ -121,7 +131,29 @@ def parse():
     p.add_argument("--per-call", action="store_true",
                    help="submit one process_device call per step from Python (default: process_device_steps)")
     p.add_argument("--spawn-probe", action="store_true", help=argparse.SUPPRESS)
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu_baseline, args.pmc, args.kt = True, "off", "off"
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all ranks' files together
+DUMP_SEED = 2024
+
+
+def dump_outputs(directory: str, y, rank: int, world: int) -> None:
+    """--dump-outputs: the last timed step's output block (what a caller of
+    process_device_steps finds in the step's output buffer), f32
+    [channels][block], as DIR/y.npy (DIR/y.rank<r>.npy per rank when N>1).  A
+    block larger than this rank's share of DUMP_MAX_BYTES is written as a
+    fixed, seeded sample of its elements (flat, in index order)."""
+    a = np.ascontiguousarray(y.detach().cpu().numpy(), dtype=np.float32)
+    keep = DUMP_MAX_BYTES // max(world, 1) // a.itemsize
+    if a.size > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=keep, replace=False))
+        a = a.reshape(-1)[idx]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "y.npy" if world == 1 else f"y.rank{rank}.npy"), a)
 
 
 def free_port() -> int:
@@ -426,6 +458,10 @@ def main():
 
     if not torch.isfinite(yout).all():
         raise SystemExit("non-finite output")
+    if args.dump_outputs and not args.pmc_inner:
+        if args.steps < 1:
+            raise SystemExit("bench.py: --dump-outputs needs at least one timed step")
+        dump_outputs(args.dump_outputs, yout[(args.warmup + args.steps - 1) % ring], rank, world)
 
     total_samples = world * C * B * args.steps  # the ranks that actually ran
     value = total_samples / elapsed / 1e6

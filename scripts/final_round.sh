@@ -6,7 +6,7 @@ set -u
 tag=$1
 scripts/gpu_step.sh ${tag}_gputest 600 python -u -m pytest tests -m gpu -q --timeout 120 --timeout-method thread || exit $?
 grep -q " passed" gpurun_out/${tag}_gputest.log && ! grep -q "failed" gpurun_out/${tag}_gputest.log || exit 5
-scripts/gpu_step.sh ${tag}_bench 300 python bench.py || exit $?
+scripts/gpu_step.sh ${tag}_bench 300 python bench.py --full || exit $?
 scripts/gpu_step.sh ${tag}_bench1000 300 python bench.py --steps 1000 --warmup 200 --no-cpu-baseline --pmc off || exit $?
 scripts/profile.sh $tag || exit $?
 scripts/gpu_step.sh ${tag}_configs 600 python scripts/bench_configs.py --configs 3,5,2u,2m --pmc || exit $?

@@ -5,6 +5,11 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
+from common import assert_close
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -28,6 +33,47 @@ def test_launcher_world_size_wins():
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
     assert lines == [{"rank": 0, "local_rank": 0, "world": 1}]  # one process runs, one rank is reported
     assert "running 1 rank" in r.stderr
+
+
+def test_full_and_dump_outputs_are_options():
+    r = _run(["--gpus", "1", "--full", "--dump-outputs", "unused", "--spawn-probe"])
+    assert r.returncode == 0, r.stderr
+    assert [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")] == [{"rank": 0, "local_rank": 0, "world": 1}]
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_timed_step(amd, oracle_mod, tmp_path):
+    """A plain run (no --full) times exactly --steps steps, runs no baseline or
+    profiler pass, and --dump-outputs writes the last timed step's output block:
+    block warmup + steps - 1 of every channel's stream (the ring's dry blocks in
+    turn), against the oracle.  S = 67: the lookahead step with all three
+    anchor levels."""
+    from fftconv_amd import shard
+
+    C, B, L, ring, warmup, steps = 6, 256, 17000, 4, 5, 7
+    out = tmp_path / "dump"
+    r = _run(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--channels", str(C), "--block", str(B),
+              "--ir", str(L), "--ring", str(ring), "--dump-outputs", str(out)])
+    assert r.returncode == 0, r.stderr
+    lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = lines[0]
+    assert line["steps"] == steps and line["warmup"] == warmup and line["dtype"] == "f32"
+    assert line["ms_per_step"] > 0 and line["unit"] == "MSamples/s" and line["higher_is_better"] is True
+    # value = samples per second of the timed steps (ms_per_step is rounded to 1e-5 ms)
+    assert abs(line["value"] - C * B / line["ms_per_step"] / 1e3) <= 1e-2 * line["value"]
+    assert line["cpu_baseline"] is None and line["roofline"]["traffic"] is None
+    assert line["roofline"]["rocprof_calls"] == 0
+    assert sorted(p.name for p in out.iterdir()) == ["y.npy"]
+    y = np.load(out / "y.npy")
+    assert y.dtype == np.float32 and y.shape == (C, B)
+    hs = shard.synth_irs(range(C), L)
+    dry = shard.synth_dry(range(C), ring, B)
+    for c in range(C):
+        ref = oracle_mod.FFTConvolver.init(hs[c], B, L)
+        for i in range(warmup + steps):
+            exp = ref.process(dry[i % ring, c])
+        assert_close(y[c], exp, what=f"channel {c}")
 
 
 def test_failing_rank_fails_the_job():
