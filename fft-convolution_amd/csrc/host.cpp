@@ -248,6 +248,24 @@ struct PinnedStage {
 
 int lg_tables(int dev, int log2m, LgTab *out);
 
+// What an owner adds to one UniformCore::process_device call (none by default)
+struct StepOpts {
+    // crossfade fusion on the lookahead step (ProcArgs::la_mix); the caller
+    // only passes these when the call takes the lookahead launch
+    int la_mix = 0;
+    const CrossfadeMixArgs *mix = nullptr;
+    float *mix_tab = nullptr;
+    // recorded once the call's outputs are final, before the far-row window
+    // anchor that follows a one-block step (the two-stage head reads the
+    // tail's output, not its windows)
+    hipEvent_t after_step = nullptr;
+    bool narrow = false;  // 2048 <= B <= 8192: 256-thread step workgroups (ProcArgs::narrow)
+    // a two-stage tail's one-block step: arrive on this signal with this
+    // value (ProcArgs::sig, sig_mode 1); null = none
+    unsigned *sig_arrive = nullptr;
+    unsigned sig_arrive_val = 0;
+};
+
 // ---------------------------------------------------------------------------
 // UniformCore -- a batch of FFTConvolver instances
 // ---------------------------------------------------------------------------
@@ -311,10 +329,6 @@ struct UniformCore {
     // gw_p = the split row (0 = off), gwin = [C][P][B], gw_t = one-block
     // steps so far (the anchor class of the next one)
     bool gw_ok = false;
-    bool narrow = false;  // 2048 <= B <= 8192: 256-thread step workgroups (ProcArgs::narrow)
-    // (a two-stage tail's one-block step: arrive on this signal, ProcArgs::sig; null = none)
-    unsigned *sig_arrive = nullptr;
-    unsigned sig_arrive_val = 0;
     int gw_p = 0;
     DevPtr<float2> gwin;
     unsigned long long gw_t = 0;
@@ -636,14 +650,8 @@ struct UniformCore {
         return FFTCONV_OK;
     }
 
-    // la_mix / mix / mix_tab: crossfade fusion on the lookahead step (ProcArgs::la_mix);
-    // the caller only passes them when this call takes the lookahead launch
-    // after_step (optional): recorded once the call's outputs are final, before
-    // the far-row window anchor that follows a one-block step (the two-stage
-    // head reads the tail's output, not its windows)
     int process_device(const float *din, size_t is, float *dout, size_t os, size_t n, hipStream_t s,
-                       int la_mix = 0, const CrossfadeMixArgs *mix = nullptr, float *mix_tab = nullptr,
-                       hipEvent_t after_step = nullptr) {
+                       const StepOpts &o = {}) {
         if (n > (size_t)INT32_MAX) return fail(FFTCONV_E_UNSUPPORTED, "process length exceeds 2^31-1");
         if (n == 0 || C == 0) return FFTCONV_OK;
         ProcArgs a{};
@@ -658,21 +666,21 @@ struct UniformCore {
             // bit-identical to one call per block; a channel off the lookahead
             // path runs the whole call (:222-294) in the first launch
             const size_t m = n / B;
-            if (m > 1 && la_mix) return fail(FFTCONV_E_INVALID, "crossfade lookahead launch of more than one block");
+            if (m > 1 && o.la_mix) return fail(FFTCONV_E_INVALID, "crossfade lookahead launch of more than one block");
             for (size_t k = 0; k < m; ++k) {
                 if (int r = la_job(a.job[0], din + k * B, is, dout + k * B, os, B, s)) return r;
                 a.job[0].mcall = (int)m;
                 a.job[0].mk = (int)k;
                 if (int r = la_fill(a, s)) return r;
-                if (la_mix && mix) {
-                    a.la_mix = la_mix;
-                    a.mix = *mix;
-                    a.mix_tab = mix_tab;
+                if (o.la_mix && o.mix) {
+                    a.la_mix = o.la_mix;
+                    a.mix = *o.mix;
+                    a.mix_tab = o.mix_tab;
                 }
                 HIP_TRY(launch_process_la(log2b, a, (int)C, s));
                 la_advance();
             }
-            if (after_step) HIP_TRY(hipEventRecord(after_step, s));
+            if (o.after_step) HIP_TRY(hipEventRecord(o.after_step, s));
             return FFTCONV_OK;
         }
         if (la_W) la_all = true;  // this launch drops every window
@@ -682,11 +690,11 @@ struct UniformCore {
             ++la_t;
         }
         lg_fill(a, n);
-        a.narrow = narrow ? 1 : 0;
+        a.narrow = o.narrow ? 1 : 0;
         a.gw_p = gw_p;  // (every launch: the split order)
-        if (sig_arrive && n == B && !large) {
-            a.sig = sig_arrive;
-            a.sig_val = sig_arrive_val;
+        if (o.sig_arrive && n == B && !large) {
+            a.sig = o.sig_arrive;
+            a.sig_val = o.sig_arrive_val;
             a.sig_mode = 1;
         }
         if (gw_p && n == B && gw_windows_allowed()) {
@@ -695,14 +703,14 @@ struct UniformCore {
             a.gw = gwin.p;
             a.gw_t = (int)(gw_t % (unsigned long long)gw_p);
             HIP_TRY(launch_process(log2b, a, (int)C, s));
-            if (after_step) HIP_TRY(hipEventRecord(after_step, s));
+            if (o.after_step) HIP_TRY(hipEventRecord(o.after_step, s));
             a.sig_mode = 0;  // (the anchor does not arrive)
             HIP_TRY(launch_gw_anchor(log2b, a, (int)C, s));
             ++gw_t;
             return FFTCONV_OK;
         }
         HIP_TRY(launch_process(log2b, a, (int)C, s));
-        if (after_step) HIP_TRY(hipEventRecord(after_step, s));
+        if (o.after_step) HIP_TRY(hipEventRecord(o.after_step, s));
         return FFTCONV_OK;
     }
 
@@ -825,6 +833,117 @@ struct UniformCore {
 };
 
 // ---------------------------------------------------------------------------
+// TailOrder -- the order between a two-stage's tail steps (side stream) and
+// the head work that reads their output.
+// The head of the period after a tail's period reads that tail's output.
+// Instead of a barrier packet on the head's stream at every period end
+// (hipStreamWaitEvent: ~7 us of cfg3's ~240 us period, r6p), the next run
+// waits on the device (ProcArgs::sig): tail step k releases tsig[1] = k, and
+// `pend` names the tail the next head work must follow (0 = none); every
+// other path waits on that tail's event ev_tk[k & 1].
+// ---------------------------------------------------------------------------
+struct TailOrder {
+    DevPtr<unsigned> tsig;  // {arrivals, last tail done, wait timeouts, -}
+    // ev_main: the period's tail_input is complete (the tail may start);
+    // ev_tk[k & 1]: tail k's step (its output, what the next period reads);
+    // ev_tail_done: everything of the last tail, its window anchor included
+    hipEvent_t ev_main = nullptr, ev_tk[2] = {nullptr, nullptr}, ev_tail_done = nullptr;
+    bool tk_sig[2] = {false, false};  // tail k arrives on tsig
+    unsigned tseq = 0, pend = 0;
+    bool tail_in_flight = false;
+
+    ~TailOrder() {
+        for (hipEvent_t e : {ev_main, ev_tk[0], ev_tk[1], ev_tail_done})
+            if (e) (void)hipEventDestroy(e);
+    }
+
+    // The events order kernels on this device only (no host wait reads what
+    // they guard), so they carry no system-scope fence: with it, cfg3
+    // one-launch-per-call periods ran at 21.5 us per call on one box (head
+    // launches held for 456 us beside the tail), without it 6.6 us
+    // (profiles/r6/r6b).
+    int create(hipStream_t stream) {
+        const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
+        HIP_TRY(hipEventCreateWithFlags(&ev_main, evf));
+        for (auto &e : ev_tk) HIP_TRY(hipEventCreateWithFlags(&e, evf));
+        if (int r = tsig.alloc(4)) return r;
+        HIP_TRY(hipMemsetAsync(tsig.p, 0, tsig.bytes(), stream));
+        tseq = pend = 0;
+        HIP_TRY(hipEventCreateWithFlags(&ev_tail_done, evf));
+        return FFTCONV_OK;
+    }
+
+    // head work on stream s follows the pending tail: the event wait (every
+    // path but a run)
+    int follow(hipStream_t s) {
+        if (pend) HIP_TRY(hipStreamWaitEvent(s, ev_tk[pend & 1], 0));
+        pend = 0;
+        return FFTCONV_OK;
+    }
+    // a run is about to launch on stream s: it waits for the pending tail on
+    // the device when that tail arrives on tsig, else s takes the event wait
+    int follow_in_run(ProcArgs &a, hipStream_t s) {
+        if (pend && tk_sig[pend & 1]) {
+            a.sig = tsig.p;
+            a.sig_val = pend;
+            a.sig_mode = 2;
+            pend = 0;
+            return FFTCONV_OK;
+        }
+        return follow(s);
+    }
+
+    // the period ended: the head work after this reads the tail in flight
+    void period_ended() {
+        if (tail_in_flight) pend = tseq;
+    }
+
+    // A tail step is about to be launched on stream ts, behind ev_main
+    // (`recorded`: a kernel's completion on s records it, else a marker on s
+    // here).  Fills the step's sequence number (never 0 = none), where it
+    // arrives (`arrives`: on tsig, else on its event only) and the event
+    // recorded after it.
+    // (the next period waits for the tail's output only, not for its window
+    // anchor: 19 us of cross-queue wait behind the anchor, r5p; starting the
+    // tail before the flush gained nothing, r5s)
+    int tail_begin(hipStream_t s, hipStream_t ts, bool recorded, bool arrives, StepOpts &o) {
+        if (!recorded) HIP_TRY(hipEventRecord(ev_main, s));
+        HIP_TRY(hipStreamWaitEvent(ts, ev_main, 0));
+        const unsigned seq = tseq + 1 == 0 ? 1 : tseq + 1;
+        o.sig_arrive = arrives ? tsig.p : nullptr;
+        o.sig_arrive_val = seq;
+        o.after_step = ev_tk[seq & 1];
+        return FFTCONV_OK;
+    }
+    // that step (and its anchor) is enqueued on ts: commit what tail_begin handed out
+    int tail_launched(hipStream_t ts, const StepOpts &o) {
+        tk_sig[o.sig_arrive_val & 1] = o.sig_arrive != nullptr;
+        tseq = o.sig_arrive_val;
+        HIP_TRY(hipEventRecord(ev_tail_done, ts));
+        tail_in_flight = true;
+        return FFTCONV_OK;
+    }
+
+    // every tail has finished once `stream` has drained; a run that gave up
+    // waiting for its tail (never expected) is an error
+    int finish(hipStream_t stream) const {
+        if (tail_in_flight) HIP_TRY(hipStreamWaitEvent(stream, ev_tail_done, 0));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (tsig.n) {
+            unsigned to = 0;
+            HIP_TRY(hipMemcpy(&to, tsig.p + 2, sizeof(unsigned), hipMemcpyDeviceToHost));
+            if (to) return fail(FFTCONV_E_DEVICE, "a two-stage run timed out waiting for its tail step");
+        }
+        return FFTCONV_OK;
+    }
+    // (after finish: no tail to follow)
+    void reset() {
+        tail_in_flight = false;
+        pend = 0;
+    }
+};
+
+// ---------------------------------------------------------------------------
 // TwoStageCore -- TwoStageFFTConvolver (src/fft_convolver.rs:323-512)
 // ---------------------------------------------------------------------------
 struct TwoStageCore {
@@ -842,58 +961,18 @@ struct TwoStageCore {
     // read one whole tail period later (after the next swap), which is the
     // reference's "might be done in some background thread" (:478).
     hipStream_t side = nullptr;
-    // an unmasked side stream for the tail of a period whose calls ran as
-    // multi-call launches (process_device_steps, upols_run_kernel): those
-    // head workgroups stay resident for the whole run, so the tail may use
-    // every CU beside them (cfg3: 5.34 us per step unmasked vs 9.26 on one
-    // unit, while one launch per call is fastest on one unit: 7.18 vs 8.07;
-    // profiles/r5/r5f_*).  null when `side` is unmasked already.
-    hipStream_t side_open = nullptr;
-    bool period_runs = false;  // this period's calls went through multi-call launches
-    hipStream_t last_ts = nullptr;  // the side stream of the last tail
-    // ev_tail: the tail's step (its output, what the next period reads);
-    // ev_tail_done: everything of it, its window anchor included (quiesce)
-    hipEvent_t ev_main = nullptr, ev_tail = nullptr, ev_tail_done = nullptr;
-    bool tail_in_flight = false;
-    // The head of the period after a tail's period reads that tail's output.
-    // Instead of a barrier packet on the head's stream at every period end
-    // (hipStreamWaitEvent: ~7 us of cfg3's ~240 us period, r6p), the next
-    // run waits on the device (ProcArgs::sig): tail step k releases
-    // tsig[1] = k, and `pend` names the tail the next head work must follow
-    // (0 = none); every other path waits on that tail's event ev_tk[k & 1].
-    DevPtr<unsigned> tsig;  // {arrivals, last tail done, wait timeouts, -}
-    hipEvent_t ev_tk[2] = {nullptr, nullptr};
-    bool tk_sig[2] = {false, false};  // tail k arrives on tsig
-    unsigned tseq = 0, pend = 0;
-    // the event wait for a pending tail, on stream s (every path but a run)
-    int resolve_pend(hipStream_t s) {
-        if (pend) HIP_TRY(hipStreamWaitEvent(s, ev_tk[pend & 1], 0));
-        pend = 0;
-        return FFTCONV_OK;
-    }
-    int ts_exp = 0;  // (timing probes, FFTCONV_TS_EXP at creation; never in tests)
-    // the tail's step on 256-thread workgroups: 0 never, 1 in periods that ran
-    // as multi-call runs, 2 always (FFTCONV_TAIL_NARROW at creation)
-    int tail_narrow = 2;
-    // the side stream confined to the tail's byte share of the CUs (off: the
-    // tail's step runs on 256-thread workgroups that fit beside the head's,
-    // and a CU-masked side stream held one handle's one-launch-per-call head
-    // launches for 456 us at a time, 21.5-22.9 us per cfg3 call, against
-    // 7.55 unmasked: profiles/r6/r6b, r6c).  FFTCONV_TAIL_MASKED=1 at creation
-    bool tail_masked = false;
-    // the side stream at the device's highest stream priority: HIP maps
-    // streams onto at most GPU_MAX_HW_QUEUES (4) hardware queues, and a side
-    // stream that shared its queue with the head's caller stream serialised
-    // the tail behind the head (the third cfg3 handle of a process ran at
-    // 5.1 us per call against 3.8); high-priority streams get queues of their
-    // own (three handles 3.75 / 3.75 / 3.75 us, profiles/r6/r6m).
-    // FFTCONV_TAIL_PRIO=0 at creation: a normal-priority side stream
-    bool tail_prio = true;
-    int run_prio = 0;  // (tuning, FFTCONV_RUN_PRIO at creation: ProcArgs::prio of the runs)
-    int run_min = 2;   // (tuning, FFTCONV_RUN_MIN at creation: shortest run of calls taken as one launch)
+    TailOrder tord;  // which tail the next head work must follow, and how it waits
+    // the tail's step on 256-thread workgroups, which fit beside the head's
+    // (tests: FFTCONV_TAIL_NARROW=0 at creation for the 512-thread reference)
+    bool tail_narrow = true;
+    // the shortest run of calls taken as one launch: a one-call run (IR rows
+    // and FDL loaded into LDS first) is slower than the per-call launch, 9.6 us
+    // per cfg3 call against 7.1 (DESIGN.md "cfg3 per call", profiles/r6/r6g2)
+    static constexpr size_t kRunMin = 2;
     // tail0 deferred to the end of its period (launch_tail0_flush): the
     // aligned calls' blocks [t0_off, t0_off + t0_n * head_bs) of tail_input
-    // still to be convolved by tail_convolver0 (FFTCONV_TAIL0_DEFER=0: off)
+    // still to be convolved by tail_convolver0 (VARIANT_T0BLOCK: off, one
+    // tail0 job per block)
     bool t0_defer = false;
     mutable size_t t0_off = 0, t0_n = 0;
     // pending blocks [0, t0_have) whose spectra a run already wrote to t0_xs
@@ -929,15 +1008,9 @@ struct TwoStageCore {
             }
         }
         if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
-        if (side_open) { (void)hipStreamSynchronize(side_open); (void)hipStreamDestroy(side_open); }
         if (stream) (void)order.drain(stream);
         head.reset(); tail0.reset(); tail.reset();  // (they borrow `stream`)
         if (stream) (void)hipStreamDestroy(stream);
-        if (ev_main) (void)hipEventDestroy(ev_main);
-        if (ev_tail) (void)hipEventDestroy(ev_tail);
-        for (auto &e : ev_tk)
-            if (e) (void)hipEventDestroy(e);
-        if (ev_tail_done) (void)hipEventDestroy(ev_tail_done);
     }
 
     float *tail_input() const { return tin_buf[tin_idx].p; }
@@ -946,102 +1019,34 @@ struct TwoStageCore {
     // (StreamOrder) and the tail convolution on the side stream
     int quiesce() const {
         if (int r = order.enter(stream)) return r;
-        if (tail_in_flight) HIP_TRY(hipStreamWaitEvent(stream, ev_tail_done, 0));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (tsig.n) {  // (a run that gave up waiting for its tail: never expected)
-            unsigned to = 0;
-            HIP_TRY(hipMemcpy(&to, tsig.p + 2, sizeof(unsigned), hipMemcpyDeviceToHost));
-            if (to) return fail(FFTCONV_E_DEVICE, "a two-stage run timed out waiting for its tail step");
-        }
-        return FFTCONV_OK;
+        return tord.finish(stream);
     }
 
-    // The side stream is confined to the first CUs of the mask, in units of
-    // ncu/8 (one XCD's worth of CUs; how the mask's CU numbering maps onto
-    // XCDs is not documented): as many units as the tail's share of the
-    // bytes streamed per tail period, at least one.  A T-block
-    // tail workgroup fills a whole CU (512 lanes x 197 VGPRs), and unconfined
-    // it locks the latency-critical head steps out of the chip for its whole
-    // duration (measured: a 197 us head step behind a 193 us tail).  With the
-    // tail's far-row windows cfg3's tail fits one unit (32 CUs):
-    // the head steps keep the rest of the chip (6.92 us per
-    // step, vs 7.29 on 36 CUs, 7.23 on 64, 7.54 on 85, and the tail no longer
-    // fits a period on 25 or fewer: profiles/r4/r4w_*, r4x_*).  Contiguous
-    // masks only: power-of-two strided masks read back fine but did not
-    // constrain dispatch (scripts/cumask_probe.hip).
+    // The side stream is unmasked: the tail's step runs on 256-thread
+    // workgroups that fit beside the head's.  Confined to the tail's byte
+    // share of the CUs (a CU-masked stream), it held one handle's
+    // one-launch-per-call head launches for 456 us at a time, 21.5-22.9 us per
+    // cfg3 call against 7.55 unmasked (profiles/r6/r6b, r6c), and a long-block
+    // tail's row pass ran at a fraction of the chip's bandwidth (head 512 /
+    // IR 200,000: 59.6 us per step on 32 CUs, 21.4 unmasked;
+    // profiles/r5/r5d_lgt_tail_units.log).
+    // It has the device's highest stream priority: HIP maps streams onto at
+    // most GPU_MAX_HW_QUEUES (4) hardware queues, and a normal-priority side
+    // stream that shared its queue with the head's caller stream serialised
+    // the tail behind the head (the third cfg3 handle of a process ran at
+    // 5.1 us per call against 3.8); high-priority streams get queues of their
+    // own (three handles 3.75 / 3.75 / 3.75 us, profiles/r6/r6m).
     int create_side_stream() {
-        int ncu = 0;
-        HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-        int cus = 0;  // 0 = unmasked
-        // A long-block tail (T > 2^kMaxLog2Fused, large.hip) is unmasked: its
-        // passes are many short 256-lane workgroups that leave room for the
-        // head steps, and confined by its byte share its row pass ran at a
-        // fraction of the chip's bandwidth (head 512 / IR 200,000: 59.6 us per
-        // step on one unit of 32 CUs, 28.7 on 3 units, 21.4 unmasked;
-        // profiles/r5/r5d_lgt_tail_units.log)
-        if (tail && ncu >= 8 && !tail->large && tail_masked) {
-            // bytes per tail period in B-bin rows: the tail's step (with windows:
-            // P-1 near rows of H and X, one window row, and 1/P of an anchor's
-            // S H rows, S X rows and P window rows) against T/h head steps
-            const double P = tail->gw_p;
-            const double tail_rows = P > 0 ? (2 * (P - 1) + 1 + (2 * tail->S + P) / P) / 2 : (double)tail->S;
-            const double tail_b = tail_rows * (double)tail->B;
-            const double per_b = tail_b + (double)(T / std::max<size_t>(head_bs, 1)) *
-                                              (double)((head ? head->S * head->B : 0) + (tail0 ? tail0->S * tail0->B : 0));
-            const int nx = std::min(7, std::max(1, (int)std::lround(8.0 * tail_b / std::max(per_b, 1.0))));
-            cus = nx * (ncu / 8);
-        }
-        // (tuning, read once per handle at creation: FFTCONV_TAIL_CU_DIV=k
-        // confines the tail to ncu/k CUs instead, 1 = unmasked;
-        // FFTCONV_TAIL_CU_UNITS=n to n units of ncu/8, 8 = unmasked)
-        if (const char *e = getenv("FFTCONV_TAIL_CU_DIV")) {
-            const int k = std::max(1, atoi(e));
-            cus = k <= 1 ? 0 : std::max(1, ncu / k);
-        }
-        const bool knob = getenv("FFTCONV_TAIL_CU_DIV") || getenv("FFTCONV_TAIL_CU_UNITS");
-        if (const char *e = getenv("FFTCONV_TAIL_CU_UNITS")) {
-            const int n = std::min(8, std::max(1, atoi(e)));
-            cus = n >= 8 ? 0 : n * (ncu / 8);
-        }
-        if (cus > 0 && cus < ncu && !knob)  // (a tuning knob governs every period)
-            HIP_TRY(hipStreamCreateWithFlags(&side_open, hipStreamNonBlocking));
-        if (cus <= 0 || cus >= ncu) {
-            if (tail_prio) {
-                int least = 0, greatest = 0;
-                HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-                HIP_TRY(hipStreamCreateWithPriority(&side, hipStreamNonBlocking, greatest));
-            } else {
-                HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
-            }
-            return FFTCONV_OK;
-        }
-        std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
-        for (int cu = 0; cu < cus; ++cu) mask[cu / 32] |= 1u << (cu % 32);
-        HIP_TRY(hipExtStreamCreateWithCUMask(&side, (uint32_t)mask.size(), mask.data()));
+        int least = 0, greatest = 0;
+        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIP_TRY(hipStreamCreateWithPriority(&side, hipStreamNonBlocking, greatest));
         return FFTCONV_OK;
     }
 
     int alloc_buffers() {
-        if (const char *e = getenv("FFTCONV_TS_EXP")) ts_exp = atoi(e);
-        if (const char *e = getenv("FFTCONV_TAIL_NARROW")) tail_narrow = atoi(e);
-        if (const char *e = getenv("FFTCONV_TAIL_MASKED")) tail_masked = atoi(e) != 0;
-        if (const char *e = getenv("FFTCONV_TAIL_PRIO")) tail_prio = atoi(e) != 0;
-        if (const char *e = getenv("FFTCONV_RUN_PRIO")) run_prio = atoi(e);
-        if (const char *e = getenv("FFTCONV_RUN_MIN")) run_min = std::max(1, atoi(e));
+        if (const char *e = getenv("FFTCONV_TAIL_NARROW")) tail_narrow = atoi(e) != 0;
         if (int r = create_side_stream()) return r;
-        // The period events order kernels on this device only (no host wait
-        // reads what they guard), so they carry no system-scope fence: with
-        // it, cfg3 one-launch-per-call periods ran at 21.5 us per call on one
-        // box (head launches held for 456 us beside the tail), without it
-        // 6.6 us (profiles/r6/r6b).  (FFTCONV_TS_EXP bit 2: the fence back)
-        const unsigned evf = hipEventDisableTiming | ((ts_exp & 4) ? 0u : hipEventDisableSystemFence);
-        HIP_TRY(hipEventCreateWithFlags(&ev_main, evf));
-        HIP_TRY(hipEventCreateWithFlags(&ev_tail, evf));
-        for (auto &e : ev_tk) HIP_TRY(hipEventCreateWithFlags(&e, evf));
-        if (int r = tsig.alloc(4)) return r;
-        HIP_TRY(hipMemsetAsync(tsig.p, 0, tsig.bytes(), stream));
-        tseq = pend = 0;
-        HIP_TRY(hipEventCreateWithFlags(&ev_tail_done, evf));
+        if (int r = tord.create(stream)) return r;
         for (auto *b : {&out0, &pre0, &out1, &pre1, &tin_buf[0], &tin_buf[1]}) {
             if (int r = b->alloc(C * T)) return r;
             if (b->n) HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes(), stream));
@@ -1134,10 +1139,7 @@ struct TwoStageCore {
             tail.reset(new (std::nothrow) UniformCore());
             if (!tail) return fail(FFTCONV_E_NOMEM, "out of host memory");
             tail->parent_stream = stream;
-            // one full-block call per period: far-row windows (tuning, read at
-            // creation: FFTCONV_TAIL_GW=0 turns them off)
-            const char *gwe = getenv("FFTCONV_TAIL_GW");
-            tail->gw_ok = !gwe || atoi(gwe) != 0;
+            tail->gw_ok = true;  // one full-block call per period: far-row windows
             st = slice(2 * T, tl, tmp);
             if (int r = tail->init(dev, C, tmp.data(), tl, st, T, tl)) return r;
         }
@@ -1153,46 +1155,67 @@ struct TwoStageCore {
     int end_of_period(hipStream_t s) {
         // ev_main (the tail may start) recorded by the flush kernel's own
         // completion (hipExtLaunchKernel) instead of a marker packet after it
-        // (cfg3 A/B 3.669 -> 3.645 us per call, r6p); FFTCONV_TS_EXP bit 4: the marker
-        const bool ev_on_flush = !(ts_exp & 16) && t0_n > 0 && tail && !(ts_exp & 8);
-        if (int r = flush_t0(s, ev_on_flush ? ev_main : nullptr)) return r;  // (tail_output0 is complete before the swap)
+        // (cfg3 A/B 3.669 -> 3.645 us per call, r6p)
+        const bool ev_on_flush = t0_n > 0 && tail;
+        if (int r = flush_t0(s, ev_on_flush ? tord.ev_main : nullptr)) return r;  // (tail_output0 is complete before the swap)
         std::swap(tail_precalculated0, tail_output0);                         // :473-475
         std::swap(tail_precalculated, tail_output);                           // :483
         // work after this point reads the swapped-in tail_precalculated: it is
-        // the previous period's tail result, which the next head work waits
-        // for (`pend`: a run on the device, every other path on its event)
-        // (FFTCONV_TS_EXP bit 0, timing probes only: no wait -- racy)
-        if (int r = resolve_pend(s)) return r;  // (a period of one call: the previous one's)
-        if (tail_in_flight && !(ts_exp & 1)) pend = tseq;
-        if (tail && !(ts_exp & 8)) {  // :484-485 (FFTCONV_TS_EXP bit 3, timing probes only: no tail at all)
-            hipStream_t ts = period_runs && side_open ? side_open : side;
-            if (!ev_on_flush) HIP_TRY(hipEventRecord(ev_main, s));  // this period's tail_input is complete
-            HIP_TRY(hipStreamWaitEvent(ts, ev_main, 0));
-            // ev_main follows the previous tail's step only (ev_tail): its
-            // window anchor ran on its own side stream, so a tail on the other
-            // one starts after that too
-            if (tail_in_flight && ts != last_ts) HIP_TRY(hipStreamWaitEvent(ts, ev_tail_done, 0));
-            // (the next period waits for the tail's output only, not for its
-            // window anchor: 19 us of cross-queue wait behind the anchor, r5p;
-            // starting the tail before the flush gained nothing, r5s)
-            tail->narrow = (tail_narrow == 2 || (tail_narrow == 1 && period_runs)) && !tail->large;
-            const unsigned seq = tseq + 1 == 0 ? 1 : tseq + 1;  // (0 = none)
-            const bool use_sig = !tail->large && !(ts_exp & 32);  // (FFTCONV_TS_EXP bit 5: events only)
-            tail->sig_arrive = use_sig ? tsig.p : nullptr;
-            tail->sig_arrive_val = seq;
-            const int rr = tail->process_device(tail_input(), T, tail_output, T, T, ts, 0, nullptr, nullptr, ev_tk[seq & 1]);
-            tail->sig_arrive = nullptr;
-            if (rr) return rr;
-            tk_sig[seq & 1] = use_sig;
-            tseq = seq;
-            HIP_TRY(hipEventRecord(ev_tail_done, ts));
-            tail_in_flight = true;
-            last_ts = ts;
+        // the previous period's tail result, which the next head work waits for
+        if (int r = tord.follow(s)) return r;  // (a period of one call: the previous one's)
+        tord.period_ended();
+        if (tail) {  // :484-485
+            StepOpts o;
+            o.narrow = tail_narrow && !tail->large;
+            // (a long-block tail's passes do not arrive on the signal words)
+            if (int r = tord.tail_begin(s, side, ev_on_flush, !tail->large, o)) return r;
+            if (int r = tail->process_device(tail_input(), T, tail_output, T, T, side, o)) return r;
+            if (int r = tord.tail_launched(side, o)) return r;
         }
-        period_runs = false;
         tin_idx ^= 1;  // the next period fills the other buffer while the tail reads this one
         tail_input_fill = 0;                                                   // :488-491
         precalculated_pos = 0;
+        return FFTCONV_OK;
+    }
+
+    // An aligned call: a whole head block on a block boundary of the period
+    // (one sub-chunk, and tail0 consumes exactly this block), with the
+    // sub-chunk epilogue fused into the head's launch.
+    bool aligned(size_t len) const {
+        return len == head_bs && tail_input_fill % head_bs == 0 && tail_input_fill + len <= T &&
+               head->log2b <= kMaxLog2Fused;
+    }
+    // the head launch of an aligned call (the first of a run's calls)
+    ProcArgs aligned_args(const float *din, size_t is, float *dout, size_t os) const {
+        ProcArgs a{};
+        a.job[0] = head->job(din, is, dout, os, head_bs);                   // :417
+        a.job[0].add0 = tail_precalculated0 + precalculated_pos;            // :439-445
+        a.job[0].add1 = tail_precalculated + precalculated_pos;             // :448-454
+        a.job[0].add_stride = (long long)T;
+        a.job[0].tin = tail_input() + tail_input_fill;                     // :459-461
+        a.job[0].tin_stride = (long long)T;
+        a.njobs = 1;
+        a.tw = head->tw.p;
+        return a;
+    }
+    // (FFTCONV_PROC_TRACE timelines: a per-call launch, a run's last call per wave)
+    int aligned_trace(ProcArgs &a, hipStream_t s) {
+        if (!head->trace_slots || head->la_W) return FFTCONV_OK;
+        if (int r = head->trace_fill(a, s)) return r;
+        ++head->la_t;
+        return FFTCONV_OK;
+    }
+    // the head launch of n aligned calls is enqueued (it writes their
+    // tail_input, so tail0's deferred blocks are counted only now, :464-472);
+    // a run that ends the period ends it as a per-call aligned call does
+    int aligned_done(size_t n, hipStream_t s) {
+        if (tail0 && t0_defer) {
+            if (t0_n == 0) t0_off = tail_input_fill;
+            t0_n += n;
+        }
+        precalculated_pos += n * head_bs;
+        tail_input_fill += n * head_bs;
+        if (tail_input_fill == T) return end_of_period(s);
         return FFTCONV_OK;
     }
 
@@ -1200,40 +1223,17 @@ struct TwoStageCore {
     int process_device(const float *din, size_t is, float *dout, size_t os, size_t len, hipStream_t s) {
         if (len > head_bs) return fail(FFTCONV_E_INVALID, "assertion failed: input.len() <= self.head_block_size");
         if (len == 0 || C == 0) return FFTCONV_OK;
-        if (int r = resolve_pend(s)) return r;
-        if (len == head_bs && tail_input_fill % head_bs == 0 && tail_input_fill + len <= T &&
-            head->log2b <= kMaxLog2Fused) {
-            // aligned call: one sub-chunk, and tail0 consumes exactly this block.
+        if (int r = tord.follow(s)) return r;
+        if (aligned(len)) {
             // One launch: head (+ the sub-chunk epilogue) and tail0 as two jobs.
-            ProcArgs a{};
-            a.job[0] = head->job(din, is, dout, os, len);                       // :417
-            a.job[0].add0 = tail_precalculated0 + precalculated_pos;            // :439-445
-            a.job[0].add1 = tail_precalculated + precalculated_pos;             // :448-454
-            a.job[0].add_stride = (long long)T;
-            a.job[0].tin = tail_input() + tail_input_fill;                     // :459-461
-            a.job[0].tin_stride = (long long)T;
-            a.njobs = 1;
-            const bool defer_block = tail0 && t0_defer;                        // :464-472, deferred
-            if (tail0 && !defer_block) {                                        // :464-472
+            ProcArgs a = aligned_args(din, is, dout, os);
+            if (tail0 && !t0_defer) {                                           // :464-472
                 a.job[1] = tail0->job(din, is, tail_output0 + tail_input_fill, T, head_bs);
                 a.njobs = 2;
             }
-            a.tw = head->tw.p;
-            if (head->trace_slots && !head->la_W) {  // (FFTCONV_PROC_TRACE timelines)
-                if (int r = head->trace_fill(a, s)) return r;
-                ++head->la_t;
-            }
+            if (int r = aligned_trace(a, s)) return r;
             HIP_TRY(launch_process(head->log2b, a, (int)C, s));
-            if (defer_block) {  // (counted once the head launch that writes its tail_input is enqueued)
-                if (t0_n == 0) t0_off = tail_input_fill;
-                ++t0_n;
-            }
-            precalculated_pos += len;
-            tail_input_fill += len;
-            if (tail_input_fill == T) {
-                if (int r = end_of_period(s)) return r;
-            }
-            return FFTCONV_OK;
+            return aligned_done(1, s);
         }
         if (int r = flush_t0(s)) return r;  // (the sub-chunk loop runs tail0 per block)
         if (int r = head->process_device(din, is, dout, os, len, s)) return r;   // :417
@@ -1272,21 +1272,11 @@ struct TwoStageCore {
                              size_t len, size_t steps, hipStream_t s) {
         size_t k = 0;
         while (k < steps) {
-            const bool aligned = len == head_bs && tail_input_fill % head_bs == 0 && tail_input_fill + len <= T &&
-                                 head->log2b <= kMaxLog2Fused;
-            const size_t left = aligned ? (T - tail_input_fill) / head_bs : 0;
+            const size_t left = aligned(len) ? (T - tail_input_fill) / head_bs : 0;
             const size_t nrun = std::min(steps - k, left);
-            if (aligned && nrun >= (size_t)run_min && t0_defer && tail0 && run_supported(head->log2b) &&
+            if (nrun >= kRunMin && t0_defer && tail0 && run_supported(head->log2b) &&
                 nrun <= (size_t)INT32_MAX && in_step <= (size_t)LLONG_MAX && out_step <= (size_t)LLONG_MAX) {
-                ProcArgs a{};
-                a.job[0] = head->job(din + k * in_step, is, dout + k * out_step, os, len);  // :417
-                a.job[0].add0 = tail_precalculated0 + precalculated_pos;                // :439-445
-                a.job[0].add1 = tail_precalculated + precalculated_pos;                 // :448-454
-                a.job[0].add_stride = (long long)T;
-                a.job[0].tin = tail_input() + tail_input_fill;                         // :459-461
-                a.job[0].tin_stride = (long long)T;
-                a.njobs = 1;
-                a.tw = head->tw.p;
+                ProcArgs a = aligned_args(din + k * in_step, is, dout + k * out_step, os);
                 // the run's block spectra double as tail0's pending-block
                 // spectra while every pending block so far has one
                 const bool t0spec = t0_have == t0_n && t0_n + nrun <= t0_nmax;
@@ -1295,33 +1285,14 @@ struct TwoStageCore {
                     a.job[0].t0x_stride = (long long)(t0_nmax * head_bs);
                     a.job[0].t0m = t0_miss.p;  // (a call that cannot write its spectrum flags the channel)
                 }
-                a.prio = run_prio;
                 a.run_lds_rows = run_lds_rows(head->log2b, (int)head->S);
-                if (pend && tk_sig[pend & 1]) {  // (the run waits for the tail on the device)
-                    a.sig = tsig.p;
-                    a.sig_val = pend;
-                    a.sig_mode = 2;
-                    pend = 0;
-                } else if (int r = resolve_pend(s)) {
-                    return r;
-                }
-                if (head->trace_slots) {  // (FFTCONV_PROC_TRACE: the run's last call, per wave)
-                    if (int r = head->trace_fill(a, s)) return r;
-                    ++head->la_t;
-                }
+                if (int r = tord.follow_in_run(a, s)) return r;
+                if (int r = aligned_trace(a, s)) return r;
                 RunSteps r{(long long)in_step, (long long)out_step, (int)nrun};
                 HIP_TRY(launch_process_run(head->log2b, a, r, (int)C, s));
-                period_runs = true;
-                if (t0_n == 0) t0_off = tail_input_fill;  // :464-472, deferred
-                t0_n += nrun;
                 if (t0spec) t0_have += nrun;
-                precalculated_pos += nrun * len;
-                tail_input_fill += nrun * len;
+                if (int r = aligned_done(nrun, s)) return r;
                 k += nrun;
-                // a run that ends the period ends it as a per-call aligned call does
-                if (tail_input_fill == T) {
-                    if (int r = end_of_period(s)) return r;
-                }
                 continue;
             }
             if (int r = process_device(din + k * in_step, is, dout + k * out_step, os, len, s)) return r;
@@ -1353,8 +1324,7 @@ struct TwoStageCore {
             if (b->n) HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes(), stream));
         tail_input_fill = 0;
         precalculated_pos = 0;
-        tail_in_flight = false;
-        pend = 0;  // (quiesce waited for every tail)
+        tord.reset();  // (quiesce waited for every tail)
         t0_n = t0_have = 0;  // (the deferred blocks' state is reset with everything else)
         if (t0_miss.n) HIP_TRY(hipMemsetAsync(t0_miss.p, 0, t0_miss.bytes(), stream));
         HIP_TRY(hipStreamSynchronize(stream));
@@ -1716,8 +1686,13 @@ struct CrossfadeCore {
                 // once into mix_tab, B's epilogue mixes A's block (buf_a) with
                 // its own straight into the output -- no mix launch, no buf_b
                 const CrossfadeMixArgs mx = mix_args(dout, os, out_len);
-                if (int r = a->process_device(din, is, buf_a.p, m, m, s, 1, &mx, mix_tab.p)) return r;
-                if (int r = b->process_device(din, is, dout, os, m, s, 2, &mx, mix_tab.p)) {
+                StepOpts o;
+                o.mix = &mx;
+                o.mix_tab = mix_tab.p;
+                o.la_mix = 1;
+                if (int r = a->process_device(din, is, buf_a.p, m, m, s, o)) return r;
+                o.la_mix = 2;
+                if (int r = b->process_device(din, is, dout, os, m, s, o)) {
                     poisoned = true;
                     return r;
                 }
@@ -2093,15 +2068,13 @@ T *make_or_null(int r, T *p) {
     return p;
 }
 
-// A caller's stream argument: NULL is HIP's null (legacy default) stream, as
-// in every HIP API (fftconv.h "Streams"); StreamOrder orders it after the
-// handle's own non-blocking streams, and nothing on it runs ahead of them.
-hipStream_t pick(void *s, hipStream_t) { return (hipStream_t)s; }
-
 }  // namespace
 
 // ===========================================================================
 // C ABI
+// A caller's stream argument: NULL is HIP's null (legacy default) stream, as
+// in every HIP API (fftconv.h "Streams"); StreamOrder orders it after the
+// handle's own non-blocking streams, and nothing on it runs ahead of them.
 // ===========================================================================
 struct fftconv_uniform { UniformCore core; };
 struct fftconv_twostage { TwoStageCore core; };
@@ -2208,7 +2181,7 @@ int fftconv_uniform_update_device(fftconv_uniform *h, const float *d_responses, 
                                   void *hip_stream) {
     if (!h) return fail(FFTCONV_E_INVALID, "null handle");
     DeviceGuard g(h->core.device);
-    hipStream_t s = pick(hip_stream, h->core.stream);
+    hipStream_t s = (hipStream_t)hip_stream;
     if (int r = h->core.order.enter(s)) return r;
     return h->core.update_device(d_responses, h->core.C == 1 ? 0 : stride, len, s);
 }
@@ -2229,7 +2202,7 @@ int fftconv_uniform_process_device(fftconv_uniform *h, const float *d_input, siz
                                    size_t out_stride, size_t len, void *hip_stream) {
     if (!h) return fail(FFTCONV_E_INVALID, "null handle");
     DeviceGuard g(h->core.device);
-    hipStream_t s = pick(hip_stream, h->core.stream);
+    hipStream_t s = (hipStream_t)hip_stream;
     if (int r = h->core.order.enter(s)) return r;
     return h->core.process_device(d_input, in_stride, d_output, out_stride, len, s);
 }
@@ -2238,7 +2211,7 @@ int fftconv_uniform_process_device_steps(fftconv_uniform *h, const float *d_inpu
                                    void *hip_stream) {
     if (!h) return fail(FFTCONV_E_INVALID, "null handle");
     DeviceGuard g(h->core.device);
-    hipStream_t s = pick(hip_stream, h->core.stream);
+    hipStream_t s = (hipStream_t)hip_stream;
     if (int r = h->core.order.enter(s)) return r;
     return h->core.process_device_steps(d_input, in_stride, in_step, d_output, out_stride, out_step, len, steps, s);
 }
@@ -2308,7 +2281,7 @@ int fftconv_twostage_process_device(fftconv_twostage *h, const float *d_input, s
                                     size_t out_stride, size_t len, void *hip_stream) {
     if (!h) return fail(FFTCONV_E_INVALID, "null handle");
     DeviceGuard g(h->core.device);
-    hipStream_t s = pick(hip_stream, h->core.stream);
+    hipStream_t s = (hipStream_t)hip_stream;
     if (int r = h->core.order.enter(s)) return r;
     return h->core.process_device(d_input, in_stride, d_output, out_stride, len, s);
 }
@@ -2317,7 +2290,7 @@ int fftconv_twostage_process_device_steps(fftconv_twostage *h, const float *d_in
                                    void *hip_stream) {
     if (!h) return fail(FFTCONV_E_INVALID, "null handle");
     DeviceGuard g(h->core.device);
-    hipStream_t s = pick(hip_stream, h->core.stream);
+    hipStream_t s = (hipStream_t)hip_stream;
     if (int r = h->core.order.enter(s)) return r;
     return h->core.process_device_steps(d_input, in_stride, in_step, d_output, out_stride, out_step, len, steps, s);
 }
@@ -2401,7 +2374,7 @@ int fftconv_crossfade_update_device(fftconv_crossfade *h, const float *d_respons
                                     void *hip_stream) {
     if (!h) return fail(FFTCONV_E_INVALID, "null handle");
     DeviceGuard g(h->core.device);
-    hipStream_t s = pick(hip_stream, h->core.stream);
+    hipStream_t s = (hipStream_t)hip_stream;
     if (int r = h->core.order.enter(s)) return r;
     return h->core.update_device(d_responses, len, h->core.C == 1 ? 0 : stride, s);
 }
@@ -2418,7 +2391,7 @@ int fftconv_crossfade_process_device(fftconv_crossfade *h, const float *d_input,
                                      size_t out_stride, size_t output_len, void *hip_stream) {
     if (!h) return fail(FFTCONV_E_INVALID, "null handle");
     DeviceGuard g(h->core.device);
-    hipStream_t s = pick(hip_stream, h->core.stream);
+    hipStream_t s = (hipStream_t)hip_stream;
     if (int r = h->core.order.enter(s)) return r;
     return h->core.process_device(d_input, in_stride, d_output, out_stride, output_len, s);
 }
@@ -2428,7 +2401,7 @@ int fftconv_crossfade_process_device_steps(fftconv_crossfade *h, const float *d_
                                    void *hip_stream) {
     if (!h) return fail(FFTCONV_E_INVALID, "null handle");
     DeviceGuard g(h->core.device);
-    hipStream_t s = pick(hip_stream, h->core.stream);
+    hipStream_t s = (hipStream_t)hip_stream;
     if (int r = h->core.order.enter(s)) return r;
     for (size_t k = 0; k < steps; ++k) {
         if (int r = h->core.process_device(d_input + k * in_step, in_stride, d_output + k * out_step, out_stride, len, s))

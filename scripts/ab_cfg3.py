@@ -4,7 +4,7 @@ cfg3 workload (TwoStageFFTConvolver, head 64 / tail 4096, IR 262144, 256
 channels; one process_device_steps call per tail period of 64 head calls).
 Each LIB may carry knobs applied before its timed runs: PATH,variant=1024,lag=8,percall=1
 (percall: one process_device_steps call per head call), and
-environment knobs read when its handle is created: PATH,FFTCONV_TAIL_LATE=1.
+environment knobs read when its handle is created: PATH,FFTCONV_TAIL_NARROW=0.
 usage: ab_cfg3.py LIB1 LIB2 ... [--rounds R] [--periods P]"""
 import argparse
 import ctypes as C
@@ -49,7 +49,7 @@ for spec in a.libs:
                                                 C.c_size_t]
     lib.fftconv_twostage_process_device_steps.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
                                                           C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p]
-    for k, v in knobs[-1].items():  # (env knobs, read at creation: FFTCONV_TAIL_LATE=1 ...)
+    for k, v in knobs[-1].items():  # (env knobs, read at creation: FFTCONV_TAIL_NARROW=0 ...)
         if k.startswith("FFTCONV_"):
             os.environ[k] = v
     h = lib.fftconv_twostage_init_batch(0, Cn, irs.ctypes.data, L, L, B, L)

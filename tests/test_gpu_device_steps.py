@@ -79,6 +79,49 @@ def test_twostage_device_steps(amd, oracle_mod, head, L):
         assert_close(y[c][m], r[m], what=f"channel {c}")
 
 
+@pytest.mark.parametrize("L,T_expect", [(20000, 2048), (120000, 4096)])
+def test_twostage_mixed_calls_and_runs(amd, oracle_mod, L, T_expect):
+    """Single calls (`process`) and runs (`process_device_steps`) alternating
+    within and across tail periods: the pending tail is followed sometimes by
+    a run's device-side wait and sometimes by the event wait of a single call
+    or of the period's end.  IR 20,000: an 8-row tail without far-row windows;
+    120,000: a 28-row tail with them (its anchor follows the step on the side
+    stream).  Bitwise equal to one `process` call per block, and the oracle."""
+    rng = np.random.default_rng(850 + L)
+    C, head = 3, 64
+    hs = np.stack([ir(rng, L) for _ in range(C)])
+    conv = amd.TwoStageFFTConvolver.init(hs, head, L, channels=C)
+    T = conv.tail_block_size
+    assert T == T_expect
+    P = T // head  # calls per tail period
+    # (kind, calls): the comments give the position in the period afterwards
+    sched = [("run", P // 3), ("one", 3),
+             ("run", P - P // 3 - 3),           # ends exactly at the period's end
+             ("one", 1),
+             ("run", P - 1),                    # ends exactly at the next period's end
+             ("run", P + P // 4),               # crosses a boundary: P // 4 into a period
+             ("one", P - P // 4 + P),           # up to the period's end, then a whole period
+             ("run", 5)]
+    K = sum(n for _, n in sched)
+    x = np.stack([white(rng, K * head) for _ in range(C)])
+    ys, k = [], 0
+    for kind, n in sched:
+        blk = x[:, k * head:(k + n) * head]
+        if kind == "run":
+            ys.append(_device_steps(conv, blk, head, n))
+        else:
+            ys += [conv.process(blk[:, j * head:(j + 1) * head]) for j in range(n)]
+        k += n
+    y = np.concatenate(ys, axis=1)
+    one = amd.TwoStageFFTConvolver.init(hs, head, L, channels=C)
+    yh = np.concatenate([one.process(x[:, j * head:(j + 1) * head]) for j in range(K)], axis=1)
+    assert np.array_equal(y, yh, equal_nan=True)
+    for c in range(C):
+        ref = oracle_mod.TwoStageFFTConvolver.init(hs[c], head, L)
+        r = np.concatenate([ref.process(x[c, j * head:(j + 1) * head]) for j in range(K)])
+        assert_close(y[c], r, what=f"channel {c}")
+
+
 NORUN = 2048  # VARIANT_NORUN: process_device_steps launches once per call
 
 

@@ -25,7 +25,7 @@ def test_cfg3_twostage_full_size(amd, oracle_mod):
     the T = 4096 tail convolver (:479-486) then runs 11 blocks, so its
     far-row windows (one anchor class in 8 per tail step, gw_anchor_kernel)
     are read by every class past entry, at cfg3 geometry with the tail on its
-    CU-masked side stream beside the head and the deferred tail0 flush.
+    high-priority side stream beside the head and the deferred tail0 flush.
     Channels 0..7 (all 8 anchor classes), 127 and 255 against
     oracle.TwoStageFFTConvolver on every call."""
     import torch
