@@ -380,4 +380,31 @@ hipError_t launch_fft_bluestein(size_t n, int log2p, bool inverse, const FftArgs
 // once into a device table (one lane), then the mix reading it
 hipError_t launch_crossfade_walk(const CrossfadeMixArgs &a, float *vtab, hipStream_t s);
 
+// MatrixConvolver (matrix.hip): one chunk -- k samples at offset `fill` of the
+// block that starts at `current` -- of every input and output.  The host keeps
+// {current, active, fill} and passes them by value.
+struct MatrixArgs {
+    const float2 *H;       // [O][I][S][B] packed IR spectra (pair o*I + i)
+    float2 *X;             // [I][S][B] one FDL per input
+    float *ovl;            // [O][B] summed overlap
+    float *ib;             // [I][B] input buffers (zero past the fill)
+    float2 *pre;           // [O][B] summed pre_multiplied of a block in progress
+    float2 *part;          // [O][P][B] split-row partial sums
+    const float2 *tw;      // W_N^k, k < N = 2B
+    const float *in;       // chunk of input 0 (+ in_stride per input)
+    long long in_stride;
+    float *out;            // chunk of output 0 (+ out_stride per output)
+    long long out_stride;
+    int I, O, S;
+    int P;                 // MAC parts (matrix_mac_parts)
+    int rpp;               // rows per part = ceil(I * (act - 1) / P)
+    int cur, act, fill, k;
+    int nt_h;              // nontemporal loads of the H stream (H larger than the Infinity Cache)
+};
+// P for a geometry and its active segments: a function of these only
+int matrix_mac_parts(int inputs, int log2b, int seg_count, int active);
+// the chunk's two launches (32 <= B <= 8192): A = R2C of every input + the
+// split-row MAC when the chunk starts a block, B = the outputs' finish
+hipError_t launch_matrix_chunk(int log2b, const MatrixArgs &a, hipStream_t s);
+
 }  // namespace fftconv

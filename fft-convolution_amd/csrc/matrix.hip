@@ -1,0 +1,355 @@
+// matrix.hip -- gfx950 kernels of the MatrixConvolver:
+//   y[o] = sum_i x[i] * h[o][i]        (o < outputs O, i < inputs I)
+// as I*O reference FFTConvolver instances (o, i) in lockstep, with ONE
+// frequency-domain delay line per input shared by every output, and the
+// spectra summed per output before ONE inverse transform.
+//
+// HBM layout (packed rows: B float2 per row, slot 0 = (DC, Nyquist)):
+//   H    float2 [O][I][S][B]  IR spectra, pair o*I + i = channel of the IR transform
+//   X    float2 [I][S][B]     one FDL per input
+//   ovl  float  [O][B]        summed overlap per output
+//   ib   float  [I][B]        input buffer per input (zero past the fill)
+//   pre  float2 [O][B]        summed pre_multiplied, kept across partial chunks
+//   part float2 [O][P][B]     split-row partial sums of one block
+//
+// A chunk (the reference's `processing`, src/fft_convolver.rs:221-227: a piece
+// of a call inside one block) is two launches on one stream; the host keeps
+// {current, active, fill} and passes them by value.  The kernel boundary is the
+// only ordering between producers and consumers: launch A's MAC workgroups
+// read FDL rows of earlier blocks only, never the row its R2C workgroups write.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "fft_lds.hpp"
+#include "kernels.hpp"
+
+namespace fftconv {
+namespace {
+
+typedef float mf32x4 __attribute__((ext_vector_type(4)));
+template <bool NTL>
+__device__ __forceinline__ float4 mld4(const float4 *p) {
+    if constexpr (NTL) {
+        const mf32x4 v = __builtin_nontemporal_load(reinterpret_cast<const mf32x4 *>(p));
+        return make_float4(v.x, v.y, v.z, v.w);
+    } else {
+        return *p;
+    }
+}
+__device__ __forceinline__ float4 madd4(float4 a, float4 b) {
+    return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+}
+
+// complex_multiply_accumulate (src/fft_convolver.rs:62-74) over one 16-byte
+// slot (2 bins); dc / ny carry the products of the packed real bins so that
+// slot 0 resolves as (DC, Nyquist).  The uniform path's accumulator.
+struct MAcc {
+    float4 a;
+    float dc, ny;
+    __device__ __forceinline__ void zero() { a = make_float4(0.f, 0.f, 0.f, 0.f); dc = ny = 0.f; }
+    __device__ __forceinline__ void mac(float4 h, float4 x) {
+        a.x = fmaf(-h.y, x.y, fmaf(h.x, x.x, a.x));
+        a.y = fmaf(h.y, x.x, fmaf(h.x, x.y, a.y));
+        a.z = fmaf(-h.w, x.w, fmaf(h.z, x.z, a.z));
+        a.w = fmaf(h.w, x.z, fmaf(h.z, x.w, a.w));
+        dc = fmaf(h.x, x.x, dc);
+        ny = fmaf(h.y, x.y, ny);
+    }
+    __device__ __forceinline__ float4 get(int slot) const { return slot == 0 ? make_float4(dc, ny, a.z, a.w) : a; }
+};
+
+// conv = pre + x (.) h for one slot, packed-aware
+__device__ __forceinline__ float4 mslot_mac(float4 pre, float4 x, float4 h, int slot) {
+    float4 r;
+    if (slot == 0) {
+        r.x = fmaf(x.x, h.x, pre.x);
+        r.y = fmaf(x.y, h.y, pre.y);
+    } else {
+        r.x = fmaf(-x.y, h.y, fmaf(x.x, h.x, pre.x));
+        r.y = fmaf(x.y, h.x, fmaf(x.x, h.y, pre.y));
+    }
+    r.z = fmaf(-x.w, h.w, fmaf(x.z, h.z, pre.z));
+    r.w = fmaf(x.w, h.z, fmaf(x.z, h.w, pre.w));
+    return r;
+}
+
+template <int LOG2B, int NT>
+struct MGeo {
+    static constexpr int B = 1 << LOG2B;
+    static constexpr int F = B / 2;                     // 16-byte slots per row
+    static constexpr int G = F >= NT ? 1 : NT / F;      // row groups of a MAC workgroup
+    static constexpr int SPT = F >= NT ? F / NT : 1;    // slots per thread
+    static constexpr int U = SPT == 1 ? 8 : (SPT == 2 ? 4 : (SPT == 4 ? 2 : 1));  // rows in flight
+    static constexpr size_t fft_bytes = 2 * (size_t)B * sizeof(float2);
+    static constexpr size_t red_bytes = G > 1 ? (size_t)NT * sizeof(float4) : 0;
+    static constexpr size_t lds_a = fft_bytes > red_bytes ? fft_bytes : red_bytes;
+    static constexpr size_t lds_b = fft_bytes;
+};
+
+// R2C role of launch A, workgroup = input i: append the chunk to ib[i],
+// transform the zero-padded buffer into X[i][current] (:229-241), clear ib[i]
+// when the block completes (:280).
+template <int LOG2B, int NT>
+__device__ __forceinline__ void matrix_r2c(const MatrixArgs &a, int i, unsigned char *smem) {
+    constexpr int B = 1 << LOG2B;
+    float2 *bufA = reinterpret_cast<float2 *>(smem);
+    float2 *bufB = bufA + B;
+    const int tid = threadIdx.x;
+    const int fill = a.fill, k = a.k;
+    const float *inc = a.in + (long long)i * a.in_stride;
+    float *ibc = a.ib + (size_t)i * B;
+    auto sample = [&](int j) -> float {
+        if (j < fill) return ibc[j];
+        if (j < fill + k) return inc[j - fill];
+        return 0.f;
+    };
+    for (int m = tid; m < B; m += NT) {
+        float2 z = make_float2(0.f, 0.f);
+        if (2 * m < B) {
+            z.x = sample(2 * m);
+            z.y = sample(2 * m + 1);
+        }
+        bufA[m] = z;
+    }
+    __syncthreads();  // (every read of ib[i] is done)
+    if (fill + k == B) {
+        if (fill > 0)
+            for (int j = tid; j < B; j += NT) ibc[j] = 0.f;
+    } else {
+        for (int j = tid; j < k; j += NT) ibc[fill + j] = inc[j];
+    }
+    const float2 *Z = lds_cfft<LOG2B, NT, false>(bufA, bufB, a.tw);
+    float2 *row = a.X + ((size_t)i * a.S + a.cur) * B;
+    for (int m = tid; m < B; m += NT) row[m] = real_post<LOG2B, NT>(Z, m, a.tw);
+}
+
+// MAC role of launch A, workgroup = (output o, part p): the rows H[o][i][s] (.)
+// X[i][(current + s) % active], s >= 1, all i, flattened i-major as
+// r = i * (active - 1) + s - 1; part p sums rows [p * rpp, (p + 1) * rpp) into
+// part[o][p].  Group g of the workgroup takes the part's rows g, g + G, ... in
+// ascending order, the groups are added in ascending g: a function of (I, B,
+// active, P) only.
+template <int LOG2B, int NT, bool NTL>
+__device__ __forceinline__ void matrix_mac(const MatrixArgs &a, int o, int p, unsigned char *smem) {
+    using Gm = MGeo<LOG2B, NT>;
+    constexpr int F = Gm::F, G = Gm::G, SPT = Gm::SPT, U = Gm::U;
+    const int tid = threadIdx.x;
+    const int f0 = G > 1 ? tid % F : tid;
+    const int g = G > 1 ? tid / F : 0;
+    const int act = a.act, am1 = act - 1;
+    const long long R = (long long)a.I * am1;
+    const long long r0 = (long long)p * a.rpp;
+    const long long r1 = r0 + a.rpp < R ? r0 + a.rpp : R;
+    DBG_CHECK(o >= 0 && o < a.O && p >= 0 && p < a.P, 51, o, p, a.O, a.P);  // (site 51: a part past `part`)
+    const int cm = a.cur % act;  // (current may exceed active after an update, :248)
+    const float4 *H4 = reinterpret_cast<const float4 *>(a.H) + (size_t)o * a.I * a.S * F;
+    const float4 *X4 = reinterpret_cast<const float4 *>(a.X);
+
+    MAcc acc[SPT];
+#pragma unroll
+    for (int s = 0; s < SPT; ++s) acc[s].zero();
+    long long r = r0 + g;
+    int i = 0, s = 1;
+    if (am1 > 0) {
+        i = (int)(r / am1);
+        s = 1 + (int)(r % am1);
+    }
+    auto advance = [&]() {
+        r += G;
+        s += G;
+        while (s > am1) {
+            s -= am1;
+            ++i;
+        }
+    };
+    auto hrow = [&]() {
+        DBG_CHECK(i >= 0 && i < a.I && s >= 1 && s < a.S, 50, i, s, a.I, a.S);  // (site 50: a MAC row past H / X)
+        return H4 + ((size_t)i * a.S + s) * F + f0;
+    };
+    auto xrow = [&]() {
+        int xi = cm + s;
+        if (xi >= act) xi -= act;
+        return X4 + ((size_t)i * a.S + xi) * F + f0;
+    };
+    while (r + (long long)(U - 1) * G < r1) {
+        float4 hv[U][SPT], xv[U][SPT];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const float4 *hp = hrow(), *xp = xrow();
+#pragma unroll
+            for (int q = 0; q < SPT; ++q) {
+                hv[u][q] = mld4<NTL>(hp + q * NT);
+                xv[u][q] = mld4<false>(xp + q * NT);
+            }
+            advance();
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int q = 0; q < SPT; ++q) acc[q].mac(hv[u][q], xv[u][q]);
+    }
+    while (r < r1) {
+        const float4 *hp = hrow(), *xp = xrow();
+#pragma unroll
+        for (int q = 0; q < SPT; ++q) acc[q].mac(mld4<NTL>(hp + q * NT), mld4<false>(xp + q * NT));
+        advance();
+    }
+
+    float4 *dst = reinterpret_cast<float4 *>(a.part) + ((size_t)o * a.P + p) * F;
+    if constexpr (G > 1) {
+        float4 *red = reinterpret_cast<float4 *>(smem);
+        red[g * F + f0] = acc[0].get(f0);
+        __syncthreads();
+        if (tid < F) {
+            float4 v = red[f0];
+#pragma unroll
+            for (int q = 1; q < G; ++q) v = madd4(v, red[q * F + f0]);
+            dst[f0] = v;
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < SPT; ++q) dst[f0 + q * NT] = acc[q].get(f0 + q * NT);
+    }
+}
+
+// Launch A: blocks [0, I) are the R2C workgroups, blocks I + o * P + p the MAC
+// workgroups (launched only for a chunk that starts a block).
+template <int LOG2B, int NT, bool NTL>
+__global__ __launch_bounds__(NT) void matrix_a_kernel(MatrixArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int b = blockIdx.x;
+    if (b < a.I) {
+        matrix_r2c<LOG2B, NT>(a, b, smem);
+    } else {
+        const int m = b - a.I;
+        matrix_mac<LOG2B, NT, NTL>(a, m / a.P, m % a.P, smem);
+    }
+}
+
+// Launch B, workgroup = output o: pre = part[o][0] + part[o][1] + ... (or the
+// kept pre[o] when the chunk starts mid-block), conv = pre + sum_i
+// X[i][current] (.) H[o][i][0] in ascending i (:256-261 summed over i), one
+// C2R with 1/N (:264, :44-46), overlap-add (:270-274), overlap saved when the
+// block completes (:283-284), pre[o] kept when it does not.
+template <int LOG2B, int NT>
+__global__ __launch_bounds__(NT) void matrix_b_kernel(MatrixArgs a) {
+    using Gm = MGeo<LOG2B, NT>;
+    constexpr int B = Gm::B, F = Gm::F, SPT = Gm::SPT;
+    constexpr int UB = SPT == 1 ? 16 : (SPT == 2 ? 8 : 4);  // terms in flight per slot
+    constexpr float invN = 1.0f / (float)(2 * B);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float2 *bufA = reinterpret_cast<float2 *>(smem);
+    float2 *bufB = bufA + B;
+    const int tid = threadIdx.x;
+    const int o = blockIdx.x;
+    const int fill = a.fill, k = a.k;
+    const bool complete = fill + k == B;
+    float4 *pre4 = reinterpret_cast<float4 *>(a.pre) + (size_t)o * F;
+    const float4 *part4 = reinterpret_cast<const float4 *>(a.part) + (size_t)o * a.P * F;
+    const float4 *H4 = reinterpret_cast<const float4 *>(a.H) + (size_t)o * a.I * a.S * F;
+    const float4 *X4 = reinterpret_cast<const float4 *>(a.X) + (size_t)a.cur * F;
+#pragma unroll
+    for (int q = 0; q < SPT; ++q) {
+        const int f = tid + q * NT;
+        if (f < F) {
+            // (both sums strictly in ascending order; the loads of UB terms are
+            // issued before their adds, so the chain waits once per UB terms)
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (fill == 0) {
+                for (int p = 0; p < a.P; p += UB) {
+                    float4 t[UB];
+#pragma unroll
+                    for (int u = 0; u < UB; ++u)
+                        if (p + u < a.P) t[u] = part4[(size_t)(p + u) * F + f];
+#pragma unroll
+                    for (int u = 0; u < UB; ++u)
+                        if (p + u < a.P) v = p + u == 0 ? t[u] : madd4(v, t[u]);
+                }
+            } else {
+                v = pre4[f];
+            }
+            if (!complete) pre4[f] = v;
+            for (int i = 0; i < a.I; i += UB / 2) {
+                float4 xs[UB / 2], hs[UB / 2];
+#pragma unroll
+                for (int u = 0; u < UB / 2; ++u) {
+                    if (i + u < a.I) {
+                        xs[u] = X4[(size_t)(i + u) * a.S * F + f];
+                        hs[u] = H4[(size_t)(i + u) * a.S * F + f];
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < UB / 2; ++u)
+                    if (i + u < a.I) v = mslot_mac(v, xs[u], hs[u], f);
+            }
+            reinterpret_cast<float4 *>(bufA)[f] = v;
+        }
+    }
+    __syncthreads();
+    for (int m = tid; m < B; m += NT) bufB[m] = real_pre<LOG2B, NT>(bufA, m, a.tw);
+    __syncthreads();
+    const float *y = reinterpret_cast<const float *>(lds_cfft<LOG2B, NT, true>(bufB, bufA, a.tw));
+    float *outc = a.out + (long long)o * a.out_stride;
+    float *ovc = a.ovl + (size_t)o * B;
+    for (int j = tid; j < k; j += NT) outc[j] = y[fill + j] * invN + ovc[fill + j];
+    if (complete) {
+        __syncthreads();  // (every overlap read above is done)
+        for (int j = tid; j < B; j += NT) ovc[j] = y[B + j] * invN;
+    }
+}
+
+constexpr int matrix_nt(int log2b) { return log2b <= 10 ? 256 : 512; }
+
+template <int LOG2B>
+hipError_t launch_matrix_t(const MatrixArgs &a, hipStream_t s) {
+    constexpr int NT = matrix_nt(LOG2B);
+    using Gm = MGeo<LOG2B, NT>;
+    auto ka = a.nt_h ? matrix_a_kernel<LOG2B, NT, true> : matrix_a_kernel<LOG2B, NT, false>;
+    auto kb = matrix_b_kernel<LOG2B, NT>;
+    if (Gm::lds_a > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void *)ka, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Gm::lds_a);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute((const void *)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Gm::lds_b);
+        if (e != hipSuccess) return e;
+    }
+    const long long grid = (long long)a.I + (a.fill == 0 ? (long long)a.O * a.P : 0);
+    hipLaunchKernelGGL(ka, dim3((unsigned)grid), dim3(NT), Gm::lds_a, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kb, dim3(a.O), dim3(NT), Gm::lds_b, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+// P: about 64 rows per part, at most 64 parts -- a function of (inputs,
+// active_seg_count) only, never of the outputs or the device, so a matrix
+// split by outputs over handles computes the same bits
+int matrix_mac_parts(int inputs, int log2b, int seg_count, int active) {
+    (void)log2b;
+    (void)seg_count;
+    const long long R = (long long)inputs * (active > 1 ? active - 1 : 0);
+    const long long p = (R + 63) / 64;
+    return (int)(p < 1 ? 1 : (p > 64 ? 64 : p));
+}
+
+hipError_t launch_matrix_chunk(int log2b, const MatrixArgs &a, hipStream_t s) {
+    if (a.I <= 0 || a.O <= 0 || a.k <= 0 || a.act <= 0 || a.P <= 0 || a.fill < 0 || a.fill + a.k > (1 << log2b) ||
+        a.cur < 0 || a.cur >= a.S || a.act > a.S)
+        return hipErrorInvalidValue;
+    if ((long long)a.I + (long long)a.O * a.P > (long long)INT32_MAX) return hipErrorInvalidValue;
+    switch (log2b) {
+        case 5: return launch_matrix_t<5>(a, s);
+        case 6: return launch_matrix_t<6>(a, s);
+        case 7: return launch_matrix_t<7>(a, s);
+        case 8: return launch_matrix_t<8>(a, s);
+        case 9: return launch_matrix_t<9>(a, s);
+        case 10: return launch_matrix_t<10>(a, s);
+        case 11: return launch_matrix_t<11>(a, s);
+        case 12: return launch_matrix_t<12>(a, s);
+        case 13: return launch_matrix_t<13>(a, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace fftconv

@@ -102,6 +102,22 @@ SIGNATURES = {
     "fftconv_crossfade_clone": (_vp, [_vp]),
     "fftconv_crossfade_destroy": (None, [_vp]),
     "fftconv_crossfade_synchronize": (_i, [_vp]),
+    "fftconv_matrix_init": (_vp, [_i, _sz, _sz, _fp, _sz, _sz, _sz, _sz]),
+    "fftconv_matrix_update": (_i, [_vp, _fp, _sz, _sz]),
+    "fftconv_matrix_update_device": (_i, [_vp, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_reset": (_i, [_vp]),
+    "fftconv_matrix_process": (_i, [_vp, _fp, _sz, _fp, _sz]),
+    "fftconv_matrix_process_device": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_process_device_steps": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _sz, _sz, _vp]),
+    "fftconv_matrix_clone": (_vp, [_vp]),
+    "fftconv_matrix_destroy": (None, [_vp]),
+    "fftconv_matrix_synchronize": (_i, [_vp]),
+    "fftconv_matrix_inputs": (_sz, [_vp]),
+    "fftconv_matrix_outputs": (_sz, [_vp]),
+    "fftconv_matrix_block_size": (_sz, [_vp]),
+    "fftconv_matrix_seg_count": (_sz, [_vp]),
+    "fftconv_matrix_mac_parts": (_i, [_vp]),
+    "fftconv_matrix_state": (_i, [_vp, C.POINTER(_sz)]),
 }
 
 
@@ -165,7 +181,7 @@ def _check(rc: int):
 def _handle(h):
     if not h:
         msg = last_error()
-        if "max_response_length" in msg or "longer" in msg:
+        if "max_response_length" in msg or "longer" in msg or "at least one input" in msg:
             raise ConvolutionPanic(msg)
         raise DeviceError(msg or "handle creation failed")
     return h
@@ -495,8 +511,83 @@ class CrossfadeConvolver(_Base):
                                   self.max_buffer_size, self.inner)
 
 
+class MatrixConvolver(_Base):
+    """Multi-input multi-output partitioned convolution (fftconv.h,
+    "MatrixConvolver"): y[o] = sum_i x[i] * h[o][i], as inputs x outputs
+    FFTConvolver instances in lockstep with one delay line per input."""
+
+    _prefix = "matrix"
+
+    def __init__(self, h, inputs: int, outputs: int):
+        super().__init__(h, inputs)
+        self.inputs = inputs
+        self.outputs = outputs
+
+    @staticmethod
+    def _pairs(responses, inputs=None, outputs=None):
+        r = _f32(responses)
+        if r.ndim != 3 or (inputs is not None and r.shape[:2] != (outputs, inputs)):
+            raise ValueError("responses must be [outputs][inputs][len]")
+        return r
+
+    @classmethod
+    def init(cls, responses, max_block_size: int, max_response_length: int, device: int = 0):
+        """responses[O][I][len]: h[o][i] is the response from input i to output o."""
+        r = cls._pairs(responses)
+        O, I, n = r.shape
+        h = lib().fftconv_matrix_init(device, I, O, _p(r), n, n, max_block_size, max_response_length)
+        return cls(_handle(h), I, O)
+
+    def update(self, responses):
+        """update() of every pair with responses[O][I][len] (whole matrix only)."""
+        r = self._pairs(responses, self.inputs, self.outputs)
+        _check(lib().fftconv_matrix_update(self._h, _p(r), r.shape[2], r.shape[2]))
+
+    def update_device(self, d_responses: int, response_len: int, stride: int = 0, stream: int = 0):
+        """update() from device memory (pair o * inputs + i at d_responses +
+        4 * pair * stride; stride 0 = one response for every pair), stream-ordered."""
+        _check(self._fn("update_device")(self._h, C.c_void_p(d_responses), response_len, stride,
+                                         C.c_void_p(stream) if stream else None))
+
+    def reset(self):
+        _check(lib().fftconv_matrix_reset(self._h))
+
+    def process(self, inp, out_len: int | None = None) -> np.ndarray:
+        """x[inputs][n] -> y[outputs][out_len or n]."""
+        x = _f32(inp)
+        if x.ndim != 2 or x.shape[0] != self.inputs:
+            raise ValueError(f"input must be [{self.inputs}][n]")
+        n_in = x.shape[1]
+        n = n_in if out_len is None else out_len
+        y = np.zeros((self.outputs, n), np.float32)
+        _check(lib().fftconv_matrix_process(self._h, _p(x), n_in, _p(y), n))
+        return y
+
+    def clone(self):
+        return MatrixConvolver(_handle(lib().fftconv_matrix_clone(self._h)), self.inputs, self.outputs)
+
+    @property
+    def block_size(self) -> int:
+        return int(lib().fftconv_matrix_block_size(self._h))
+
+    @property
+    def seg_count(self) -> int:
+        return int(lib().fftconv_matrix_seg_count(self._h))
+
+    @property
+    def mac_parts(self) -> int:
+        """Workgroups sharing one output's spectral sum, for the current active_seg_count."""
+        return int(lib().fftconv_matrix_mac_parts(self._h))
+
+    def state(self):
+        """(current, active_seg_count, input_buffer_fill) of the whole matrix."""
+        out = (C.c_size_t * 3)()
+        _check(lib().fftconv_matrix_state(self._h, out))
+        return tuple(int(v) for v in out)
+
+
 __all__ = [
-    "Fft", "FFTConvolver", "TwoStageFFTConvolver", "CrossfadeConvolver", "ConvolutionPanic",
+    "Fft", "FFTConvolver", "TwoStageFFTConvolver", "CrossfadeConvolver", "MatrixConvolver", "ConvolutionPanic",
     "NotImplementedInReference", "DeviceError", "complex_size", "compute_tail_block_size", "device_count",
     "lib", "LIB_PATH", "SIGNATURES",
 ]

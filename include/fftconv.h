@@ -60,6 +60,7 @@ enum {
 typedef struct fftconv_uniform fftconv_uniform;     /* FFTConvolver        src/fft_convolver.rs:86-307 */
 typedef struct fftconv_twostage fftconv_twostage;   /* TwoStageFFTConvolver src/fft_convolver.rs:323-512 */
 typedef struct fftconv_crossfade fftconv_crossfade; /* CrossfadeConvolver<FFTConvolver | TwoStageFFTConvolver> src/crossfade_convolver.rs:10-105 */
+typedef struct fftconv_matrix fftconv_matrix;       /* inputs x outputs FFTConvolver instances, summed per output (below) */
 
 /* ---- library ----------------------------------------------------------- */
 int fftconv_abi_version(void);
@@ -303,6 +304,68 @@ int fftconv_crossfade_is_crossfading(const fftconv_crossfade *h); /* :85-92, 1/0
 fftconv_crossfade *fftconv_crossfade_clone(const fftconv_crossfade *h);
 void fftconv_crossfade_destroy(fftconv_crossfade *h);
 int fftconv_crossfade_synchronize(fftconv_crossfade *h);
+
+/* ---- MatrixConvolver: multi-input multi-output partitioned convolution ----
+ *     y[o] = sum_i x[i] * h[o][i]        (o < outputs, i < inputs)
+ * A matrix (inputs I, outputs O, block B, max_response_length) behaves as I*O
+ * FFTConvolver instances (o, i) (src/fft_convolver.rs:86-307), all created,
+ * updated and reset together with the same response_len: instance (o, i)
+ * processes input i, output o is the sum over i of the outputs of (o, i).  The
+ * state machine of :215-295 runs in lockstep, so one {current,
+ * active_seg_count, input_buffer_fill} describes the matrix (fftconv_matrix_state).
+ * The device keeps one frequency-domain delay line per input, sums the spectra
+ * per output and runs one inverse transform per output: results equal the
+ * summed instances within f32 rounding, not bitwise.  Outputs do not depend on
+ * `outputs`: a matrix split by outputs over several handles (or GPUs) computes
+ * bit-identical rows.
+ * Two departures from the per-instance reference:
+ *  - Non-finite samples are outside the parity contract.  The per-instance
+ *    "C2R error -> zero-fill, state frozen" path (:264-267) cannot be
+ *    reproduced with a shared delay line: output values are unspecified while
+ *    a non-finite sample is inside the delay line or the overlap, the state
+ *    advances normally, and outputs are exact again once the sample has left.
+ *  - Only whole-matrix update: update() zeroes overlap and pre_multiplied per
+ *    instance (:186-188), which the matrix keeps summed per output, so a
+ *    per-pair update cannot match the definition and is not offered.
+ * Responses: pair p = o * inputs + i at responses + p * response_stride
+ * (response_stride 0 = one response for every pair).  Supported blocks:
+ * 32 <= next_power_of_two(max_block_size) <= 8192, else FFTCONV_E_UNSUPPORTED;
+ * inputs == 0, outputs == 0 or response_len > max_response_length is
+ * FFTCONV_E_INVALID; init returns NULL on error (fftconv_last_error). */
+fftconv_matrix *fftconv_matrix_init(int device, size_t inputs, size_t outputs, const float *responses,
+                                    size_t response_len, size_t response_stride, size_t max_block_size,
+                                    size_t max_response_length);
+/* :174-213 for every pair; asynchronous like fftconv_uniform_update. */
+int fftconv_matrix_update(fftconv_matrix *h, const float *responses, size_t response_len,
+                          size_t response_stride);
+int fftconv_matrix_update_device(fftconv_matrix *h, const float *d_responses, size_t response_len,
+                                 size_t response_stride, void *hip_stream);
+int fftconv_matrix_reset(fftconv_matrix *h); /* :296-306 */
+/* input [inputs][input_len], output [outputs][output_len], host memory;
+ * input_len < output_len is FFTCONV_E_INVALID. */
+int fftconv_matrix_process(fftconv_matrix *h, const float *input, size_t input_len, float *output,
+                           size_t output_len);
+/* device memory, stream-ordered: input i at d_input + i * in_stride, output o
+ * at d_output + o * out_stride (strides in floats). */
+int fftconv_matrix_process_device(fftconv_matrix *h, const float *d_input, size_t in_stride, float *d_output,
+                                  size_t out_stride, size_t len, void *hip_stream);
+/* `steps` consecutive process_device calls, call k at d_input + k * in_step /
+ * d_output + k * out_step; the same bits as the separate calls. */
+int fftconv_matrix_process_device_steps(fftconv_matrix *h, const float *d_input, size_t in_stride,
+                                        size_t in_step, float *d_output, size_t out_stride, size_t out_step,
+                                        size_t len, size_t steps, void *hip_stream);
+fftconv_matrix *fftconv_matrix_clone(const fftconv_matrix *h);
+void fftconv_matrix_destroy(fftconv_matrix *h);
+int fftconv_matrix_synchronize(fftconv_matrix *h);
+size_t fftconv_matrix_inputs(const fftconv_matrix *h);
+size_t fftconv_matrix_outputs(const fftconv_matrix *h);
+size_t fftconv_matrix_block_size(const fftconv_matrix *h);
+size_t fftconv_matrix_seg_count(const fftconv_matrix *h);
+/* workgroups that share one output's spectral sum, for the current
+ * active_seg_count: a function of (inputs, block, seg_count, active) only. */
+int fftconv_matrix_mac_parts(const fftconv_matrix *h);
+/* {current, active_seg_count, input_buffer_fill} as of the calls enqueued so far */
+int fftconv_matrix_state(const fftconv_matrix *h, size_t out3[3]);
 
 #ifdef __cplusplus
 }

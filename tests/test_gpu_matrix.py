@@ -1,0 +1,257 @@
+"""MatrixConvolver (include/fftconv.h): y[o] = sum_i x[i] * h[o][i] as
+inputs x outputs FFTConvolver instances in lockstep.  Reference: per output the
+f64 sum over i of oracle FFTConvolver instances fed the same call lengths
+(matrix_ref.SummedOracle; tests/test_matrix_ref.py puts it 1.6e-7 to 2.5e-7
+from f64 direct convolution on these shapes), tolerance common.REL_TOL."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import oracle as oracle_module
+from common import REL_TOL, assert_close
+from matrix_ref import RAGGED_64, RAGGED_256, SummedOracle, direct, make
+
+pytestmark = pytest.mark.gpu
+
+
+@functools.lru_cache(maxsize=None)
+def _case(seed, I, O, B, L, lengths):
+    """(h, x, summed-oracle output, oracle state after every call); computed
+    once per shape, shared, never written to"""
+    h, x = make(seed, I, O, L, sum(lengths))
+    ref = SummedOracle(oracle_module, h, B, L)
+    ys, states, pos = [], [], 0
+    for n in lengths:
+        ys.append(ref.process(x[:, pos:pos + n]))
+        states.append(ref.state())
+        pos += n
+    y = np.concatenate(ys, axis=1)
+    for a in (h, x, y):
+        a.setflags(write=False)
+    return h, x, y, tuple(states)
+
+
+def _run(conv, x, lengths, states=None):
+    out, pos = [], 0
+    for k, n in enumerate(lengths):
+        out.append(conv.process(x[:, pos:pos + n]))
+        if states is not None:
+            assert conv.state() == states[k], (k, conv.state(), states[k])
+        pos += n
+    return np.concatenate(out, axis=1)
+
+
+def _check_outputs(y, ref, what):
+    for o in range(ref.shape[0]):
+        assert_close(y[o], ref[o], what=f"{what} output {o}")
+
+
+def test_full_blocks(amd):
+    """I=3, O=2, B=64, L=1000 (S=16), 40 one-block calls."""
+    I, O, B, L = 3, 2, 64, 1000
+    h, x, ref, states = _case(11, I, O, B, L, (B,) * 40)
+    conv = amd.MatrixConvolver.init(h, B, L)
+    assert (conv.inputs, conv.outputs, conv.block_size, conv.seg_count) == (I, O, B, 16)
+    y = _run(conv, x, (B,) * 40, states)
+    _check_outputs(y, ref, "summed oracle")
+    _check_outputs(y, direct(oracle_module, x, h), "direct")
+
+
+@pytest.mark.parametrize("I,O,B,L,lengths", [(3, 2, 64, 1000, tuple(RAGGED_64)), (2, 2, 256, 1500, tuple(RAGGED_256))])
+def test_ragged_calls(amd, I, O, B, L, lengths):
+    """Calls that start and end anywhere: the input buffer, the kept
+    pre_multiplied sum, and calls that span several blocks."""
+    h, x, ref, states = _case(12, I, O, B, L, lengths)
+    conv = amd.MatrixConvolver.init(h, B, L)
+    y = _run(conv, x, lengths, states)
+    _check_outputs(y, ref, "summed oracle")
+
+
+@pytest.mark.parametrize("B", [32, 128, 512, 2048, 8192])
+def test_block_sizes(amd, B):
+    """The limits (32, 8192: the two-buffer LDS is full), the first 512-thread
+    size (2048) and sizes between: 5 full blocks, then calls of B - 24 and 24."""
+    L = 3 * B + 5
+    lengths = (B,) * 5 + (B - 24, 24)
+    h, x, ref, states = _case(13, 2, 2, B, L, lengths)
+    conv = amd.MatrixConvolver.init(h, B, L)
+    assert conv.seg_count == 4
+    y = _run(conv, x, lengths, states)
+    _check_outputs(y, ref, f"B={B}")
+
+
+def test_split_rows(amd):
+    """I=4, O=2, B=32, L=4096 (S=128): 508 rows per output in 8 parts, 140
+    blocks so the delay line wraps; I=1, O=2, B=64, L=200: 3 rows, one part."""
+    h, x, ref, states = _case(14, 4, 2, 32, 4096, (32,) * 140)
+    conv = amd.MatrixConvolver.init(h, 32, 4096)
+    assert conv.mac_parts >= 2
+    y = conv.process(x)
+    assert conv.state() == states[-1]
+    _check_outputs(y, ref, "split")
+    h, x, ref, states = _case(15, 1, 2, 64, 200, (64,) * 10)
+    conv = amd.MatrixConvolver.init(h, 64, 200)
+    assert conv.mac_parts == 1
+    _check_outputs(_run(conv, x, (64,) * 10, states), ref, "one part")
+
+
+def test_output_sharding_bitwise(amd):
+    """Outputs do not depend on the number of outputs: one handle against two
+    handles holding outputs 0..2 and 3..5."""
+    I, O, B, L = 3, 6, 64, 2000
+    h, x = make(16, I, O, L, 40 * B)
+    whole = amd.MatrixConvolver.init(h, B, L)
+    lo = amd.MatrixConvolver.init(h[:3], B, L)
+    hi = amd.MatrixConvolver.init(h[3:], B, L)
+    assert whole.mac_parts == lo.mac_parts == hi.mac_parts
+    yw = _run(whole, x, (B,) * 40)
+    ys = np.concatenate([_run(lo, x, (B,) * 40), _run(hi, x, (B,) * 40)], axis=0)
+    assert np.isfinite(yw).all() and np.abs(yw).max() > 0
+    assert np.array_equal(yw, ys)
+
+
+def _update_sequence(I, O, B, L):
+    """(kind, payload) steps: update at a block boundary, mid-block, a shrink
+    to 130 samples while current >= 3, then a zero-length response"""
+    rng = np.random.default_rng(17)
+    h0, x = make(17, I, O, L, 60 * B)
+    mk = lambda n: (rng.uniform(-1, 1, (O, I, n)) / np.sqrt(max(n, 1))).astype(np.float32)
+    return h0, x, [("run", (B,) * 5), ("update", mk(700)), ("run", (B,) * 3 + (20,)), ("update", mk(L)),
+                   ("run", (44,) + (B,) * 4), ("need_current", 3), ("update", mk(130)),
+                   ("run", (B, 10, 54, B, 2 * B, B)), ("update", mk(0)), ("run", (B, 30))]
+
+
+def test_update(amd):
+    I, O, B, L = 3, 2, 64, 1000
+    h0, x, seq = _update_sequence(I, O, B, L)
+    ref = SummedOracle(oracle_module, h0, B, L)
+    conv = amd.MatrixConvolver.init(h0, B, L)
+    dev = amd.MatrixConvolver.init(h0, B, L)
+    pos = 0
+    for kind, arg in seq:
+        if kind == "update":
+            ref.update(arg)
+            conv.update(arg)
+            d = torch.from_numpy(arg).to("cuda:0")
+            dev.update_device(d.data_ptr(), arg.shape[2], arg.shape[2], 0)
+            dev.synchronize()
+            assert conv.state() == dev.state() == ref.state()
+        elif kind == "need_current":
+            assert ref.state()[0] >= arg, ref.state()
+        else:
+            for n in arg:
+                blk = x[:, pos:pos + n]
+                r = ref.process(blk)
+                y = conv.process(blk)
+                yd = dev.process(blk)
+                assert conv.state() == ref.state()
+                assert np.array_equal(y, yd), "update_device differs from update"
+                if ref.state()[1] == 0:
+                    assert not y.any() and not r.any()
+                else:
+                    _check_outputs(y, r, f"after update, samples {pos}..{pos + n}")
+                pos += n
+    assert ref.state()[1] == 0
+
+
+def test_reset_and_clone(amd):
+    I, O, B, L = 3, 2, 64, 1000
+    lengths = tuple(RAGGED_64[:11])
+    h, x, ref, states = _case(12, I, O, B, L, tuple(RAGGED_64))
+    n = sum(lengths)
+    conv = amd.MatrixConvolver.init(h, B, L)
+    _run(conv, x[:, 500:], (64, 64, 17))
+    conv.reset()
+    assert conv.state() == (0, 16, 0)
+    fresh = amd.MatrixConvolver.init(h, B, L)
+    y = _run(conv, x[:, :n], lengths)
+    assert np.array_equal(y, _run(fresh, x[:, :n], lengths))
+    _check_outputs(y, ref[:, :n], "after reset")
+    # (the 11 calls end mid-block: fill != 0)
+    assert conv.state()[2] != 0
+    twin = conv.clone()
+    assert twin.state() == conv.state()
+    rest = tuple(RAGGED_64[11:])
+    ya = _run(conv, x[:, n:], rest)
+    yb = _run(twin, x[:, n:], rest)
+    assert np.array_equal(ya, yb)
+    _check_outputs(ya, ref[:, n:], "after clone")
+
+
+@pytest.mark.parametrize("n,K", [(64, 30), (40, 30)])
+def test_process_device_steps(amd, n, K):
+    """30 steps of a block and 30 steps of 40 samples at B = 64, on a torch
+    side stream with padded rows; a consumer on that stream reads the result
+    without a host synchronisation."""
+    I, O, B, L = 3, 2, 64, 1000
+    h, x = make(18, I, O, L, K * n)
+    dev = torch.device("cuda:0")
+    pad_in, pad_out = n + 5, n + 3
+    xs = np.zeros((K, I, pad_in), np.float32)
+    xs[:, :, :n] = x.reshape(I, K, n).transpose(1, 0, 2)
+    xd = torch.from_numpy(xs).to(dev)
+    s = torch.cuda.Stream(dev)
+    s.wait_stream(torch.cuda.current_stream())
+    a = amd.MatrixConvolver.init(h, B, L)
+    b = amd.MatrixConvolver.init(h, B, L)
+    ya = torch.full((K, O, pad_out), -7.0, device=dev)
+    yb = torch.full((K, O, pad_out), -7.0, device=dev)
+    s.wait_stream(torch.cuda.current_stream())
+    a.process_device_steps(xd.data_ptr(), pad_in, I * pad_in, ya.data_ptr(), pad_out, O * pad_out, n, K,
+                           s.cuda_stream)
+    with torch.cuda.stream(s):
+        doubled = ya * 2.0  # (ordered by the stream alone)
+    for k in range(K):
+        b.process_device(xd[k].data_ptr(), pad_in, yb[k].data_ptr(), pad_out, n, s.cuda_stream)
+    s.synchronize()
+    assert a.state() == b.state()
+    ya_h, yb_h = ya.cpu().numpy(), yb.cpu().numpy()
+    assert np.array_equal(ya_h, yb_h)
+    assert np.array_equal(doubled.cpu().numpy(), ya_h * 2.0)
+    assert (ya_h[:, :, n:] == -7.0).all()  # (the padding is untouched)
+    y = ya_h[:, :, :n].transpose(1, 0, 2).reshape(O, K * n)
+    ref = SummedOracle(oracle_module, h, B, L).run(x, (n,) * K)
+    _check_outputs(y, ref, "device steps")
+
+
+def test_non_finite_sample_leaves(amd):
+    """A NaN in input 1 at block 5 (I=2, O=2, B=64, L=500, S=8): from sample
+    nan_idx + (S + 2) * B on, outputs are finite and within tolerance of f64
+    direct convolution with that sample set to 0."""
+    I, O, B, L, S = 2, 2, 64, 500, 8
+    h, x = make(19, I, O, L, 30 * B)
+    nan_idx = 5 * B + 10
+    xn = x.copy()
+    xn[1, nan_idx] = np.nan
+    conv = amd.MatrixConvolver.init(h, B, L)
+    y = _run(conv, xn, (B,) * 30)
+    x0 = x.copy()
+    x0[1, nan_idx] = 0.0
+    ref = direct(oracle_module, x0, h)
+    first = nan_idx + (S + 2) * B
+    assert np.isfinite(y[:, first:]).all()
+    peak = np.abs(ref).max()
+    assert np.abs(y[:, first:] - ref[:, first:]).max() <= REL_TOL * peak
+    assert conv.state() == (S - 30 % S if 30 % S else 0, S, 0)
+
+
+def test_errors(amd):
+    h, x = make(20, 2, 2, 100, 64)
+    with pytest.raises(amd.ConvolutionPanic):
+        amd.MatrixConvolver.init(h, 64, 99)                       # response_len > max_response_length
+    with pytest.raises(amd.ConvolutionPanic):
+        amd.MatrixConvolver.init(np.zeros((2, 0, 8), np.float32), 64, 8)   # inputs == 0
+    with pytest.raises(amd.ConvolutionPanic):
+        amd.MatrixConvolver.init(np.zeros((0, 2, 8), np.float32), 64, 8)   # outputs == 0
+    for bad in (16, 16384):
+        with pytest.raises(amd.DeviceError, match="block size"):
+            amd.MatrixConvolver.init(h, bad, 100)
+    conv = amd.MatrixConvolver.init(h, 64, 100)
+    with pytest.raises(amd.ConvolutionPanic):
+        conv.process(x[:, :10], out_len=11)                       # input_len < output_len
+    with pytest.raises(amd.ConvolutionPanic):
+        conv.update(np.zeros((2, 2, 101), np.float32))
+    assert conv.state() == (0, 2, 0)
+    assert conv.process(x, out_len=32).shape == (2, 32)
