@@ -1958,7 +1958,10 @@ struct MatrixCore {
         const size_t R = I * (act - 1);
         a.rpp = (int)ceil_div(R, (size_t)a.P);
         a.act = (int)act;
-        a.nt_h = H.bytes() > ((size_t)256 << 20) ? 1 : 0;
+        {  // (automatic: H past the Infinity Cache; a set kernel variant decides by its VARIANT_NT bit)
+            const int var = get_variant();
+            a.nt_h = (var < 0 ? H.bytes() > ((size_t)256 << 20) : (var & VARIANT_NT) != 0) ? 1 : 0;
+        }
         size_t processed = 0;
         while (processed < n) {                                     // :222-294
             const size_t k = std::min(n - processed, B - fill);     // :224-227

@@ -399,7 +399,8 @@ struct MatrixArgs {
     int P;                 // MAC parts (matrix_mac_parts)
     int rpp;               // rows per part = ceil(I * (act - 1) / P)
     int cur, act, fill, k;
-    int nt_h;              // nontemporal loads of the H stream (H larger than the Infinity Cache)
+    int nt_h;              // nontemporal loads of the H stream (H larger than the Infinity Cache; with a
+                           // kernel variant set, its VARIANT_NT bit instead -- same bits either way)
 };
 // P for a geometry and its active segments: a function of these only
 int matrix_mac_parts(int inputs, int log2b, int seg_count, int active);

@@ -73,6 +73,8 @@ __device__ __forceinline__ float4 mslot_mac(float4 pre, float4 x, float4 h, int 
     return r;
 }
 
+// (tests/matrix_paths.py mirrors these constants, matrix_nt, UB and the P rule
+// to prove which loops each test shape runs: change them together)
 template <int LOG2B, int NT>
 struct MGeo {
     static constexpr int B = 1 << LOG2B;

@@ -56,6 +56,38 @@ def direct(oracle, x, h) -> np.ndarray:
     return y
 
 
+class BlockModel:
+    """f64 model of the reference's uniformly partitioned convolution for all
+    [O][I] pairs at once (numpy.fft over the batch), full blocks only and a
+    constant active segment count: for matrices with too many pairs for
+    SummedOracle.  update() keeps the delay line and clears the overlap, as
+    FFTConvolver::update does."""
+
+    def __init__(self, h, block, max_len):
+        self.B = block
+        self.S = -(-max_len // block)
+        self.update(h)
+        self.X = [np.zeros((self.I, block + 1), np.complex128) for _ in range(self.S)]
+
+    def update(self, h):
+        h = np.asarray(h, np.float64)
+        self.O, self.I, n = h.shape
+        assert -(-n // self.B) == self.S
+        hp = np.zeros((self.O, self.I, self.S * self.B))
+        hp[:, :, :n] = h
+        self.H = np.fft.rfft(hp.reshape(self.O, self.I, self.S, self.B), 2 * self.B, axis=3)
+        self.ovl = np.zeros((self.O, self.B))
+
+    def process_block(self, x) -> np.ndarray:
+        """x[I][B] -> f64 [O][B]"""
+        self.X = [np.fft.rfft(np.asarray(x, np.float64), 2 * self.B, axis=1)] + self.X[:-1]
+        spec = sum(np.einsum("oif,if->of", self.H[:, :, s], self.X[s]) for s in range(self.S))
+        y = np.fft.irfft(spec, 2 * self.B, axis=1)
+        out = y[:, :self.B] + self.ovl
+        self.ovl = y[:, self.B:]
+        return out
+
+
 def make(seed, inputs, outputs, length, samples):
     """(h[O][I][length], x[I][samples]) from common.ir / common.white"""
     rng = np.random.default_rng(seed)

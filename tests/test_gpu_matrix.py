@@ -1,8 +1,9 @@
 """MatrixConvolver (include/fftconv.h): y[o] = sum_i x[i] * h[o][i] as
 inputs x outputs FFTConvolver instances in lockstep.  Reference: per output the
 f64 sum over i of oracle FFTConvolver instances fed the same call lengths
-(matrix_ref.SummedOracle; tests/test_matrix_ref.py puts it 1.6e-7 to 2.5e-7
-from f64 direct convolution on these shapes), tolerance common.REL_TOL."""
+(matrix_ref.SummedOracle; tests/test_matrix_ref.py puts it 1.6e-7 to 3.3e-7
+from f64 direct convolution on these shapes), tolerance common.REL_TOL.  The
+path shapes (matrix_paths.SHAPES) are compared with f64 direct convolution."""
 import functools
 
 import numpy as np
@@ -10,8 +11,9 @@ import pytest
 import torch
 
 import oracle as oracle_module
-from common import REL_TOL, assert_close
-from matrix_ref import RAGGED_64, RAGGED_256, SummedOracle, direct, make
+from common import REL_TOL, assert_close, max_rel_err
+from matrix_paths import CAPPED, SHAPES, capped_lengths, parts, shape_blocks, shape_id, shape_len, walk
+from matrix_ref import RAGGED_64, RAGGED_256, BlockModel, SummedOracle, direct, make
 
 pytestmark = pytest.mark.gpu
 
@@ -255,3 +257,201 @@ def test_errors(amd):
         conv.update(np.zeros((2, 2, 101), np.float32))
     assert conv.state() == (0, 2, 0)
     assert conv.process(x, out_len=32).shape == (2, 32)
+
+
+# ---------------------------------------------------------------------------
+# Path coverage (matrix_paths): shapes at which matrix_mac's unrolled loop, its
+# hand-over to the tail loop, several parts at every block size, the P cap and
+# matrix_b_kernel's chunked sums run; tests/test_matrix_ref.py proves on the
+# CPU that each shape reaches the path it is listed for.
+# ---------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def _direct_case(seed, I, O, L, n):
+    """(h, x, f64 direct convolution); computed once per shape, never written to"""
+    h, x = make(seed, I, O, L, n)
+    ref = direct(oracle_module, x, h)
+    for a in (h, x, ref):
+        a.setflags(write=False)
+    return h, x, ref
+
+
+def _check_ref(y, ref, what):
+    """finite, non-zero (unless the reference is), within tolerance; prints the
+    error so a run shows how much of REL_TOL each shape uses"""
+    assert np.isfinite(y).all(), what
+    assert np.abs(y).max() > 0 or not ref.any(), what
+    print(f"{what}: max_rel_err {max_rel_err(y, ref):.3e}")
+    _check_outputs(y, ref, what)
+
+
+@pytest.mark.parametrize("s", SHAPES, ids=shape_id)
+def test_paths(amd, s):
+    """S + 3 full blocks of every path shape in one call against f64 direct
+    convolution: the delay line wraps, every MAC row contributes.  One
+    dropped, doubled or misplaced row of R moves an output by about
+    max|ref| / sqrt(R) (1 % at R = 8220), a part left out of the finish
+    kernel's sum by sqrt(1 / P): both far above REL_TOL."""
+    L, n = shape_len(s), shape_blocks(s) * s.B
+    h, x, ref = _direct_case(21, s.I, s.O, L, n)
+    conv = amd.MatrixConvolver.init(h, s.B, L)
+    assert (conv.block_size, conv.seg_count) == (s.B, s.S)
+    assert conv.mac_parts == walk(s.B, s.I, s.S).P
+    y = conv.process(x)
+    assert conv.state() == (-shape_blocks(s) % s.S, s.S, 0)
+    _check_ref(y, ref, shape_id(s))
+
+
+@pytest.mark.parametrize("s", CAPPED, ids=shape_id)
+def test_paths_ragged_capped(amd, s):
+    """The two shapes at the P cap (64 parts, more than 64 rows each): one
+    call of S blocks, then calls that start and end anywhere -- the kept
+    pre_multiplied sum of 64 parts."""
+    lengths = capped_lengths(s)
+    h, x, ref, states = _case(22, s.I, s.O, s.B, shape_len(s), lengths)
+    conv = amd.MatrixConvolver.init(h, s.B, shape_len(s))
+    assert conv.mac_parts == 64
+    y = _run(conv, x, lengths, states)
+    _check_ref(y, ref, "ragged " + shape_id(s))
+
+
+def test_update_changes_parts(amd):
+    """Updates that change P (B 32, I 4, O 2, S 128; `part` is sized for
+    P = 8): 68 blocks (current 60), update to 40 segments (P = 3, current >=
+    active) and 45 blocks, back to the full length (P = 8) and 130 blocks, 20
+    samples (one segment, no MAC rows) and 3 blocks, length 0 and one call.
+    A second handle follows through update_device."""
+    I, O, B, L = 4, 2, 32, 4096
+    rng = np.random.default_rng(23)
+    h0, x = make(23, I, O, L, (68 + 45 + 130 + 3 + 1) * B)
+    mk = lambda n: (rng.uniform(-1, 1, (O, I, n)) / np.sqrt(max(n, 1))).astype(np.float32)
+    ref = SummedOracle(oracle_module, h0, B, L)
+    conv = amd.MatrixConvolver.init(h0, B, L)
+    dev = amd.MatrixConvolver.init(h0, B, L)
+    assert conv.mac_parts == dev.mac_parts == 8
+    pos = 0
+
+    def run(calls, what):
+        nonlocal pos
+        for n in calls:
+            blk = x[:, pos:pos + n]
+            r = ref.process(blk)
+            y = conv.process(blk)
+            yd = dev.process(blk)
+            assert conv.state() == dev.state() == ref.state()
+            assert np.array_equal(y, yd), "update_device differs from update"
+            if ref.state()[1] == 0:
+                assert not y.any() and not r.any()
+            else:
+                _check_ref(y, r, f"{what}, samples {pos}..{pos + n}")
+            pos += n
+
+    def update(hn, P):
+        ref.update(hn)
+        conv.update(hn)
+        d = torch.from_numpy(hn).to("cuda:0")
+        dev.update_device(d.data_ptr(), hn.shape[2], hn.shape[2], 0)
+        dev.synchronize()
+        assert conv.state() == dev.state() == ref.state()
+        assert conv.mac_parts == dev.mac_parts == P == parts(I, ref.state()[1])
+
+    run((B,) * 4 + (64 * B,), "P = 8")
+    assert ref.state()[0] >= 60
+    update(mk(40 * B - 5), 3)
+    assert ref.state()[0] >= ref.state()[1] == 40
+    run((B,) * 25 + (20 * B,), "P = 3")
+    assert ref.state()[0] < 40  # (current came back inside the active segments)
+    update(mk(L), 8)
+    run((B,) * 2 + (128 * B,), "P = 8 again")
+    update(mk(20), 1)
+    run((B,) * 3, "one segment")
+    update(mk(0), 1)
+    run((B,), "no response")
+    assert ref.state()[1] == 0 and pos == x.shape[1]
+
+
+def test_many_pairs(amd):
+    """More than 32768 (o, i) pairs (I = 2, O = 16400, B 64, L 100, S 2; H is
+    33 MiB): the IR transform runs in two slabs of pairs.  Four one-block
+    calls, an update to a new response, two more blocks, against the f64
+    block model (matrix_ref.BlockModel, validated in tests/test_matrix_ref.py);
+    the outputs of the second slab (o >= 16384) are asserted on their own."""
+    I, O, B, L = 2, 16400, 64, 100
+    rng = np.random.default_rng(24)
+    mk = lambda: (rng.uniform(-1, 1, (O, I, L)) / np.sqrt(L)).astype(np.float32)
+    h, h2 = mk(), mk()
+    x = rng.uniform(-1, 1, (I, 6 * B)).astype(np.float32)
+    assert O * I > 32768
+    ref = BlockModel(h, B, L)
+    conv = amd.MatrixConvolver.init(h, B, L)
+    assert (conv.seg_count, conv.mac_parts) == (2, 1)
+
+    def blocks(ks, what):
+        for k in ks:
+            blk = x[:, k * B:(k + 1) * B]
+            r = ref.process_block(blk)
+            y = conv.process(blk)
+            assert np.isfinite(y).all() and np.abs(y[16384:]).max() > 0
+            peak = np.abs(r).max()
+            e_lo = np.abs(y[:16384] - r[:16384]).max() / peak
+            e_hi = np.abs(y[16384:] - r[16384:]).max() / peak
+            print(f"many pairs {what} block {k}: first slab {e_lo:.3e}, second slab {e_hi:.3e}")
+            assert e_hi <= REL_TOL, f"{what} block {k}: second slab of pairs (outputs >= 16384) {e_hi:.3e}"
+            assert e_lo <= REL_TOL, f"{what} block {k}: first slab of pairs {e_lo:.3e}"
+
+    blocks(range(4), "init")
+    # (the block model itself, on outputs of both slabs, against f64 direct convolution)
+    sel = [0, 16383, 16384, 16399]
+    m = BlockModel(h[sel], B, L)
+    ym = np.concatenate([m.process_block(x[:, k * B:(k + 1) * B]) for k in range(4)], axis=1)
+    assert max_rel_err(ym, direct(oracle_module, x[:, :4 * B], h[sel])) <= 1e-12
+    ref.update(h2)
+    conv.update(h2)
+    blocks(range(4, 6), "after update")
+    assert conv.state() == (0, 2, 0)
+
+
+def test_zero_length_response_device(amd):
+    """process_device with no active segment (update to length 0): exactly n
+    zeros per output row of a padded output, the padding and the state
+    untouched."""
+    I, O, B, L, n = 3, 2, 64, 100, 40
+    h, x = make(25, I, O, L, 3 * B + 17)
+    conv = amd.MatrixConvolver.init(h, B, L)
+    y = _run(conv, x, (B, B, B, 17))
+    assert np.abs(y).max() > 0
+    conv.update(np.zeros((O, I, 0), np.float32))
+    state = conv.state()
+    assert state == (1, 0, 17)
+    dev = torch.device("cuda:0")
+    xd = torch.ones((I, n + 5), device=dev)
+    yd = torch.full((O, n + 3), -7.0, device=dev)
+    conv.process_device(xd.data_ptr(), n + 5, yd.data_ptr(), n + 3, n)
+    conv.synchronize()
+    torch.cuda.synchronize()
+    out = yd.cpu().numpy()
+    assert (out[:, :n] == 0.0).all()
+    assert (out[:, n:] == -7.0).all()
+    assert conv.state() == state
+
+
+@pytest.mark.parametrize("s", [s for s in SHAPES if (s.B, s.I) in ((128, 11), (1024, 5))], ids=shape_id)
+def test_nontemporal_instantiation(amd, s):
+    """matrix_a_kernel<..., true> (nontemporal H loads; chosen automatically
+    only above 256 MiB of H) through the kernel-variant knob, at a shape with
+    row groups (G = 4) and one with SPT = 2: bitwise equal to the plain-load
+    instantiation and within tolerance of f64 direct convolution."""
+    L, n = shape_len(s), shape_blocks(s) * s.B
+    h, x, ref = _direct_case(21, s.I, s.O, L, n)
+    ys = []
+    for v in (2, 0):
+        amd.set_kernel_variant(v)
+        try:
+            conv = amd.MatrixConvolver.init(h, s.B, L)
+            ys.append(conv.process(x))
+        finally:
+            amd.set_kernel_variant(-1)
+    for y, what in zip(ys, ("nontemporal", "plain")):
+        _check_ref(y, ref, f"{what} {shape_id(s)}")
+        assert np.abs(y).max() > 0
+    assert np.array_equal(ys[0], ys[1])
