@@ -481,7 +481,8 @@ struct UniformCore {
     // FDL (launch_la_rebuild), as if anchored by the launch before the next
     // one; without the lookahead step (or with VARIANT_LAFULL) nothing to do
     int la_rebuild(hipStream_t s, size_t chan0, size_t nch) {
-        if (!la_W || la_parts(log2b, (int)S) != la_W || la_full_variant() || nch == 0) return FFTCONV_OK;
+        if (!la_W || la_parts(log2b, (int)S) != la_W || Variant::current().has(VARIANT_LAFULL) || nch == 0)
+            return FFTCONV_OK;
         const unsigned long long per = (unsigned long long)la_dims(log2b, (int)S).per_all;
         ProcArgs a{};
         a.job[0] = job(nullptr, 0, nullptr, 0, B);
@@ -527,7 +528,7 @@ struct UniformCore {
             const size_t sst = (stride == 0 && C > 1) ? 0 : ir_len;
             if (int r = ir_from_device(0, C, staging.p, sst, len, ir_len, false, stream)) return r;
         }
-        if (la_W && !la_full_variant()) {  // the first process launch is a steady-state one too
+        if (la_W && !Variant::current().has(VARIANT_LAFULL)) {  // the first process launch is a steady-state one too
             if (int r = la_rebuild(stream, 0, C)) return r;
             la_all = false;
         }
@@ -573,7 +574,7 @@ struct UniformCore {
         HIP_TRY(launch_reset_state(state.p, (int)C, s));
         view_ok = false;
         lg_whole = true;
-        if (la_W && !la_full_variant()) {  // windows of the zeroed FDL, in the reset
+        if (la_W && !Variant::current().has(VARIANT_LAFULL)) {  // windows of the zeroed FDL, in the reset
             la_all = false;
             return la_rebuild(s, 0, C);
         }
@@ -697,7 +698,7 @@ struct UniformCore {
             a.sig_val = o.sig_arrive_val;
             a.sig_mode = 1;
         }
-        if (gw_p && n == B && gw_windows_allowed()) {
+        if (gw_p && n == B && !Variant::current().has(VARIANT_NOGW)) {
             // a one-block step reads the live windows, then the channels of
             // class gw_t mod P anchor theirs for their next P blocks
             a.gw = gwin.p;
@@ -1054,7 +1055,7 @@ struct TwoStageCore {
         tail_output0 = out0.p; tail_precalculated0 = pre0.p;
         tail_output = out1.p; tail_precalculated = pre1.p;
         tin_idx = 0;
-        const bool defer = tail0_defer_allowed();  // (VARIANT_T0BLOCK: per-block tail0, tests)
+        const bool defer = !Variant::current().has(VARIANT_T0BLOCK);  // (per-block tail0: tests)
         t0_nmax = T / std::max<size_t>(head_bs, 1);
         t0_defer = defer && tail0 && tail0->B == head_bs &&
                    tail0_defer_supported(tail0->log2b, (int)tail0->S, (int)t0_nmax);
@@ -1660,7 +1661,8 @@ struct CrossfadeCore {
             // :72-73 on the lookahead step: each convolver's full
             // block runs its own launch of far / mid anchors and steps; then
             // the mix (:75-77)
-            if (out_len == m && la_fuse_mix_allowed() && a->la_t == b->la_t && a->la_seq == b->la_seq &&
+            const bool fuse_mix = out_len == m && !Variant::current().has(VARIANT_NOFMIX);
+            if (fuse_mix && a->la_t == b->la_t && a->la_seq == b->la_seq &&
                 a->la_all == b->la_all) {
                 // :72-77 in ONE launch: A's and B's anchors, and per channel
                 // one workgroup running A's and B's step (two chain waves)
@@ -1681,7 +1683,7 @@ struct CrossfadeCore {
                 xf.advance(out_len);
                 return FFTCONV_OK;
             }
-            if (out_len == m && la_fuse_mix_allowed()) {
+            if (fuse_mix) {
                 // the mix fused into B's launch: A's launch walks mix_value
                 // once into mix_tab, B's epilogue mixes A's block (buf_a) with
                 // its own straight into the output -- no mix launch, no buf_b
@@ -1958,10 +1960,7 @@ struct MatrixCore {
         const size_t R = I * (act - 1);
         a.rpp = (int)ceil_div(R, (size_t)a.P);
         a.act = (int)act;
-        {  // (automatic: H past the Infinity Cache; a set kernel variant decides by its VARIANT_NT bit)
-            const int var = get_variant();
-            a.nt_h = (var < 0 ? H.bytes() > ((size_t)256 << 20) : (var & VARIANT_NT) != 0) ? 1 : 0;
-        }
+        a.nt_h = Variant::current().nt_matrix(H.bytes()) ? 1 : 0;
         size_t processed = 0;
         while (processed < n) {                                     // :222-294
             const size_t k = std::min(n - processed, B - fill);     // :224-227

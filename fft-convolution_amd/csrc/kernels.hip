@@ -19,10 +19,12 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 
 #include "fft_lds.hpp"
 #include "kernels.hpp"
+#include "launch.hpp"
 #include <hip/hip_ext.h>
 
 namespace fftconv {
@@ -1935,12 +1937,7 @@ static hipError_t launch_fft_t(bool inverse, const FftArgs &a, int rows, hipStre
     constexpr int NT = LOG2M <= 6 ? 64 : 256;
     constexpr size_t lds = 2 * (size_t)(1 << LOG2M) * sizeof(float2) + 16;
     auto kern = inverse ? fft_rows_kernel<LOG2M, NT, true> : fft_rows_kernel<LOG2M, NT, false>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(rows), dim3(NT), lds, s, a);
-    return hipGetLastError();
+    return launch_dyn(kern, dim3(rows), dim3(NT), lds, s, a);
 }
 
 // ---------------------------------------------------------------------------
@@ -2478,12 +2475,19 @@ replay:
     }
 }
 
-static int g_variant = VARIANT_AUTO;
-// the scan bits 0-2 (zig-zag, nontemporal, no pipelined step) override the
-// automatic load / step policy only when one of them is set: a variant of
-// feature bits alone (bits 3-10) keeps the automatic policy
-static bool scan_variant_set() { return g_variant != VARIANT_AUTO && (g_variant & 7) != 0; }
-static int g_lag = -1;
+// The process-wide tuning knobs (variant.hpp).  Relaxed atomics: set / read
+// from any thread; a launcher reads each once.
+static std::atomic<int> g_variant{VARIANT_AUTO};
+static std::atomic<int> g_lag{-1};
+
+void set_variant(int v) { g_variant.store(v < 0 ? VARIANT_AUTO : (v & 4095), std::memory_order_relaxed); }
+Variant Variant::current() { return Variant{g_variant.load(std::memory_order_relaxed)}; }
+int get_variant() {
+    const Variant v = Variant::current();
+    return v.is_auto() ? -1 : v.bits;
+}
+void set_pipeline_lag(int rows) { g_lag.store(rows < 0 ? -1 : rows, std::memory_order_relaxed); }
+int get_pipeline_lag() { return g_lag.load(std::memory_order_relaxed); }
 
 // Pipelined step: FDL rows the three stream waves take alone while wave 0
 // runs the transform chain.  Auto: all of them -- wave 0 never streams (cfg3
@@ -2491,33 +2495,20 @@ static int g_lag = -1;
 // >= 62 1844 MS/s; the chain is the critical path, any row given to wave 0
 // lengthens it).  Never a function of the channel count, so channel shards
 // of any size stay bit-identical.
-static int pipeline_lag(int) { return g_lag >= 0 ? g_lag : (1 << 30); }
+static int pipeline_lag() {
+    const int lag = get_pipeline_lag();
+    return lag >= 0 ? lag : (1 << 30);
+}
 
-// Automatic variant: a per-step H+X stream larger than the 256 MiB Infinity
-// Cache is re-read from HBM every step whatever the load policy, and there
-// nontemporal loads stream 12-14 % faster (measured, cfg2: 137 -> 121 us);
-// a stream that stays cache-resident across steps is 1.5x faster with plain
-// loads (S = 8: 9.5 vs 14.3 us).  Both variants perform identical arithmetic,
-// so the choice never changes a result bit; zig-zag (+0.6 % on top of NT)
-// changes the summation order and is therefore opt-in only, keeping channel
-// shards bit-identical whatever the shard size.
-//
-// The pipelined full-block step pays off where a channel's FDL stream is
-// short next to its transform chain (cfg3's head, S*B = 4096: 1630 -> 1860
-// MS/s) and costs ~3 % on long ones (cfg2, S*B = 48128: the other resident
-// workgroups' streams already cover each chain, and three stream waves issue
-// fewer loads than four).  It changes the summation order, so it is chosen
-// per channel geometry (never by channel count): shards stay bit-identical.
-static int pick_variant(const ProcArgs &a, int channels, int log2b) {
-    if (scan_variant_set()) return g_variant;
+// the step's variant bits for a launch of a.njobs jobs (Variant::step_bits)
+static int pick_variant(Variant v, const ProcArgs &a, int channels, int log2b) {
     double stream = 0.0;
     long long rows = 0;
     for (int j = 0; j < a.njobs; ++j) {
-        stream += 16.0 * (double)channels * (double)a.job[j].S * (double)(1 << log2b);
+        stream += Variant::stream_bytes(channels, a.job[j].S, log2b);
         rows = std::max(rows, (long long)a.job[j].S);
     }
-    const int nt = stream > 192.0 * 1024 * 1024 ? VARIANT_NT : 0;
-    return nt | ((rows << log2b) > 16384 ? VARIANT_NOPIPE : 0) | (g_variant == VARIANT_AUTO ? 0 : g_variant);
+    return v.step_bits(stream, rows << log2b);
 }
 
 template <int LOG2B>
@@ -2530,27 +2521,12 @@ static hipError_t launch_gw_anchor_t(const ProcArgs &a, int channels, hipStream_
     ProcArgs args = a;
     args.la_channels = channels;
     const int ny = (channels - cls + kGwP - 1) / kGwP;
-    hipLaunchKernelGGL(gw_anchor_kernel<LOG2B>, dim3(F / SL, ny), dim3(256), 0, s, args);
-    return hipGetLastError();
+    return launch_dyn(gw_anchor_kernel<LOG2B>, dim3(F / SL, ny), dim3(256), 0, s, args);
 }
 
 hipError_t launch_gw_anchor(int log2b, const ProcArgs &a, int channels, hipStream_t s) {
-    switch (log2b) {
-        case 10: return launch_gw_anchor_t<10>(a, channels, s);
-        case 11: return launch_gw_anchor_t<11>(a, channels, s);
-        case 12: return launch_gw_anchor_t<12>(a, channels, s);
-        case 13: return launch_gw_anchor_t<13>(a, channels, s);
-        case 14: return launch_gw_anchor_t<14>(a, channels, s);
-        case 15: return launch_gw_anchor_t<15>(a, channels, s);
-        case 16: return launch_gw_anchor_t<16>(a, channels, s);
-        case 17: return launch_gw_anchor_t<17>(a, channels, s);
-        case 18: return launch_gw_anchor_t<18>(a, channels, s);
-        case 19: return launch_gw_anchor_t<19>(a, channels, s);
-        case 20: return launch_gw_anchor_t<20>(a, channels, s);
-        case 21: return launch_gw_anchor_t<21>(a, channels, s);
-        case 22: return launch_gw_anchor_t<22>(a, channels, s);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_log2<10, kMaxLog2Block>(log2b, hipErrorInvalidValue,
+                                            [&](auto L) { return launch_gw_anchor_t<L()>(a, channels, s); });
 }
 
 bool gw_supported(int log2b, int S) { return log2b >= 10 && log2b <= kMaxLog2Block && S >= 3 * kGwP; }
@@ -2575,51 +2551,30 @@ __global__ __launch_bounds__(256, 2) void upols_narrow_kernel(ProcArgs a) {
     if (a.sig_mode == 1) sig_arrive(a);
 }
 
+// One step launch of a kernel family kernel(ZZ, NTL) (zig-zag scan,
+// nontemporal loads: the variant's bits 0 and 1) on NT threads.
+template <int LOG2B, int NT, class Family>
+static hipError_t launch_step_t(Family kernel, bool may_pipe, const ProcArgs &a, int channels, hipStream_t s) {
+    using Y = std::true_type;
+    using N = std::false_type;
+    void (*const kern[4])(ProcArgs) = {kernel(N{}, N{}), kernel(Y{}, N{}), kernel(N{}, Y{}), kernel(Y{}, Y{})};
+    const int var = pick_variant(Variant::current(), a, channels, LOG2B);
+    ProcArgs args = a;
+    args.pipe = may_pipe && !(var & VARIANT_NOPIPE) ? 1 : 0;
+    args.lag = pipeline_lag();
+    return launch_dyn(kern[var & 3], dim3(channels, a.njobs), dim3(NT), Geo<LOG2B, NT>::lds_bytes, s, args);
+}
+
 template <int LOG2B>
 static hipError_t launch_process_t(const ProcArgs &a, int channels, hipStream_t s) {
     if constexpr (LOG2B >= 11 && LOG2B <= kMaxLog2Fused) {
-        if (a.narrow) {
-            using Gn = Geo<LOG2B, 256>;
-            auto kern = upols_narrow_kernel<LOG2B, false, false>;
-            const int var = pick_variant(a, channels, LOG2B);
-            ProcArgs args = a;
-            args.pipe = 0;
-            args.lag = pipeline_lag(LOG2B);
-            switch (var & 3) {
-                case 1: kern = upols_narrow_kernel<LOG2B, true, false>; break;
-                case 2: kern = upols_narrow_kernel<LOG2B, false, true>; break;
-                case 3: kern = upols_narrow_kernel<LOG2B, true, true>; break;
-                default: break;
-            }
-            if (Gn::lds_bytes > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)Gn::lds_bytes);
-                if (e != hipSuccess) return e;
-            }
-            hipLaunchKernelGGL(kern, dim3(channels, a.njobs), dim3(256), Gn::lds_bytes, s, args);
-            return hipGetLastError();
-        }
+        if (a.narrow)
+            return launch_step_t<LOG2B, 256>(
+                [](auto zz, auto ntl) { return upols_narrow_kernel<LOG2B, zz(), ntl()>; }, false, a, channels, s);
     }
     constexpr int PNT = proc_nt(LOG2B);
-    using Gm = Geo<LOG2B, PNT>;
-    auto kern = upols_process_kernel<LOG2B, PNT, false, false>;
-    const int var = pick_variant(a, channels, LOG2B);
-    ProcArgs args = a;
-    args.pipe = (var & VARIANT_NOPIPE) ? 0 : 1;
-    args.lag = pipeline_lag(LOG2B);
-    switch (var & 3) {
-        case 1: kern = upols_process_kernel<LOG2B, PNT, true, false>; break;
-        case 2: kern = upols_process_kernel<LOG2B, PNT, false, true>; break;
-        case 3: kern = upols_process_kernel<LOG2B, PNT, true, true>; break;
-        default: break;
-    }
-    if (Gm::lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)Gm::lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(channels, a.njobs), dim3(PNT), Gm::lds_bytes, s, args);
-    return hipGetLastError();
+    return launch_step_t<LOG2B, PNT>(
+        [](auto zz, auto ntl) { return upols_process_kernel<LOG2B, PNT, zz(), ntl()>; }, true, a, channels, s);
 }
 
 template <int LOG2B>
@@ -2628,24 +2583,18 @@ static hipError_t launch_run_t(const ProcArgs &a, const RunSteps &r, int channel
         constexpr int PNT = proc_nt(LOG2B);
         using Gm = Geo<LOG2B, PNT>;
         if (a.njobs != 1 || r.n < 1) return hipErrorInvalidValue;
-        const int var = pick_variant(a, channels, LOG2B);
+        const int var = pick_variant(Variant::current(), a, channels, LOG2B);
         if (var & 1) return hipErrorInvalidValue;  // (zig-zag order: per-call launches only)
         ProcArgs args = a;
         args.pipe = (var & VARIANT_NOPIPE) ? 0 : 1;
-        args.lag = pipeline_lag(LOG2B);
+        args.lag = pipeline_lag();
         auto kern = (var & VARIANT_NT) ? upols_run_kernel<LOG2B, PNT, true> : upols_run_kernel<LOG2B, PNT, false>;
         // (+ the run-carried spectra and the next block's transform buffers,
         // pipelined_step; + the IR rows and the FDL when they fit)
         const size_t lds = Gm::lds_bytes + 4 * (size_t)Gm::B * sizeof(float2) +
                            (size_t)a.run_lds_rows * 2 * Gm::B * sizeof(float2);
         if (a.run_lds_rows < 0 || lds > 160 * 1024) return hipErrorInvalidValue;
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kern, dim3(channels), dim3(PNT), lds, s, args, r);
-        return hipGetLastError();
+        return launch_dyn(kern, dim3(channels), dim3(PNT), lds, s, args, r);
     } else {
         return hipErrorNotSupported;
     }
@@ -2656,49 +2605,41 @@ static hipError_t launch_run_t(const ProcArgs &a, const RunSteps &r, int channel
 // only for the run-carried pipelined step (B <= 256); else 0
 int run_lds_rows(int log2b, int S) {
     if (log2b < 6 || log2b > 8 || S < 2) return 0;
-    if (g_variant != VARIANT_AUTO && (g_variant & VARIANT_NORUNLDS)) return 0;
+    if (Variant::current().has(VARIANT_NORUNLDS)) return 0;  // (not selectable through the ABI, variant.hpp)
     const size_t B = (size_t)1 << log2b;
-    const size_t base = (log2b == 6 ? Geo<6, 256>::lds_bytes : (log2b == 7 ? Geo<7, 256>::lds_bytes : Geo<8, 256>::lds_bytes)) +
-                        4 * B * sizeof(float2);
+    static_assert(proc_nt(8) == 256, "process_lds_bytes: the run kernels' 256 threads");
+    const size_t base = process_lds_bytes(log2b) + 4 * B * sizeof(float2);
     return base + (size_t)S * 2 * B * sizeof(float2) <= 96 * 1024 ? S : 0;
 }
 bool run_supported(int log2b) {
-    if (g_variant != VARIANT_AUTO && (g_variant & VARIANT_NORUN)) return false;
-    return log2b >= 6 && log2b <= 9 && !(scan_variant_set() && (g_variant & VARIANT_ZIGZAG));
+    return log2b >= 6 && log2b <= 9 && !Variant::current().has(VARIANT_NORUN | VARIANT_ZIGZAG);
 }
 hipError_t launch_process_run(int log2b, const ProcArgs &a, const RunSteps &r, int channels, hipStream_t s) {
     if (channels <= 0) return hipSuccess;
-    switch (log2b) {
-        case 6: return launch_run_t<6>(a, r, channels, s);
-        case 7: return launch_run_t<7>(a, r, channels, s);
-        case 8: return launch_run_t<8>(a, r, channels, s);
-        case 9: return launch_run_t<9>(a, r, channels, s);
-        default: return hipErrorNotSupported;
-    }
+    return dispatch_log2<6, 9>(log2b, hipErrorNotSupported,
+                               [&](auto L) { return launch_run_t<L()>(a, r, channels, s); });
 }
 
 template <int LOG2B>
 static hipError_t launch_tail0_t(const Tail0Args &a, int channels, hipStream_t s, hipEvent_t done) {
     if constexpr (LOG2B >= 6 && LOG2B <= 9) {
-        constexpr int B = 1 << LOG2B, KT = 256 / (B / 2), NT = proc_nt(LOG2B);
+        constexpr int B = 1 << LOG2B, KT = 256 / (B / 2);
         if (a.n <= 0 || a.n > a.nmax) return hipErrorInvalidValue;
         Tail0Args t = a;
-        const int var = pick_variant(a.pa, channels, LOG2B);
+        const Variant v = Variant::current();
+        const int var = pick_variant(v, a.pa, channels, LOG2B);
         t.pa.pipe = (var & VARIANT_NOPIPE) ? 0 : 1;  // (the replay path's generic step)
-        t.pa.lag = pipeline_lag(LOG2B);
+        t.pa.lag = pipeline_lag();
         // (every check before the first launch: a failure leaves the pending
         // blocks and tail0's state untouched)
         constexpr int F = B / 2, FC = F < T0_FC ? F : T0_FC;
         const size_t lds = tail0_mac_lds<LOG2B>(a.act, a.n);
         auto mk = tail0_mac_kernel<LOG2B>;
         if (lds > 160 * 1024 || (256 / FC) * T0_J < a.n) return hipErrorInvalidValue;
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)mk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
+        if (hipError_t e = lds_attr(mk, lds); e != hipSuccess) return e;
         if constexpr (LOG2B == 6) {
             // (VARIANT_T0FUSED: the five kernels instead, bit-identical)
-            if (tail0_fused_fits<LOG2B>(a.act, a.n) && !(g_variant != VARIANT_AUTO && (g_variant & VARIANT_T0FUSED))) {
+            if (tail0_fused_fits<LOG2B>(a.act, a.n) && !v.has(VARIANT_T0FUSED)) {
                 const size_t fl = tail0_fused_lds<LOG2B>(a.act, a.n);
                 auto fk = tail0_fused_kernel<LOG2B>;
                 if (hipError_t e = hipFuncSetAttribute((const void *)fk, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2742,63 +2683,33 @@ bool tail0_defer_supported(int log2b, int act, int nmax) {
 }
 hipError_t launch_tail0_flush(int log2b, const Tail0Args &a, int channels, hipStream_t s, hipEvent_t done) {
     if (channels <= 0) return hipSuccess;
-    switch (log2b) {
-        case 6: return launch_tail0_t<6>(a, channels, s, done);
-        case 7: return launch_tail0_t<7>(a, channels, s, done);
-        case 8: return launch_tail0_t<8>(a, channels, s, done);
-        case 9: return launch_tail0_t<9>(a, channels, s, done);
-        default: return hipErrorNotSupported;
-    }
+    return dispatch_log2<6, 9>(log2b, hipErrorNotSupported,
+                               [&](auto L) { return launch_tail0_t<L()>(a, channels, s, done); });
 }
 
 template <int LOG2B>
 static hipError_t launch_ir_t(const IrArgs &a, int channels, hipStream_t s) {
     if constexpr (LOG2B >= 6 && LOG2B <= 10) {
-        if (g_variant == VARIANT_AUTO || !(g_variant & VARIANT_IRBLOCK)) {
-            constexpr size_t lds = ir_wave_lds<LOG2B>();
+        if (!Variant::current().has(VARIANT_IRBLOCK)) {
             constexpr int NW = ir_nw<LOG2B>();
-            auto kern = ir_segments_wave_kernel<LOG2B>;
-            if (lds > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) return e;
-            }
-            hipLaunchKernelGGL(kern, dim3((a.S + NW * IR_SPW - 1) / (NW * IR_SPW), channels), dim3(64 * NW), lds, s, a);
-            return hipGetLastError();
+            return launch_dyn(ir_segments_wave_kernel<LOG2B>, dim3((a.S + NW * IR_SPW - 1) / (NW * IR_SPW), channels),
+                              dim3(64 * NW), ir_wave_lds<LOG2B>(), s, a);
         }
     }
     constexpr size_t lds = 2 * (size_t)(1 << LOG2B) * sizeof(float2) + 16;
-    auto kern = ir_segments_kernel<LOG2B, kNT>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(a.S, channels), dim3(kNT), lds, s, a);
-    return hipGetLastError();
+    return launch_dyn(ir_segments_kernel<LOG2B, kNT>, dim3(a.S, channels), dim3(kNT), lds, s, a);
 }
 
-#define FFTCONV_DISPATCH(FN, LOG2B, ...)                      \
-    switch (LOG2B) {                                          \
-        case 0: return FN<0>(__VA_ARGS__);                    \
-        case 1: return FN<1>(__VA_ARGS__);                    \
-        case 2: return FN<2>(__VA_ARGS__);                    \
-        case 3: return FN<3>(__VA_ARGS__);                    \
-        case 4: return FN<4>(__VA_ARGS__);                    \
-        case 5: return FN<5>(__VA_ARGS__);                    \
-        case 6: return FN<6>(__VA_ARGS__);                    \
-        case 7: return FN<7>(__VA_ARGS__);                    \
-        case 8: return FN<8>(__VA_ARGS__);                    \
-        case 9: return FN<9>(__VA_ARGS__);                    \
-        case 10: return FN<10>(__VA_ARGS__);                  \
-        case 11: return FN<11>(__VA_ARGS__);                  \
-        case 12: return FN<12>(__VA_ARGS__);                  \
-        case 13: return FN<13>(__VA_ARGS__);                  \
-        default: return hipErrorInvalidValue;                 \
-    }
+// the fused kernels' block sizes: 1 <= B <= 8192
+template <class F>
+static hipError_t dispatch_fused(int log2b, F &&f) {
+    return dispatch_log2<0, kMaxLog2Fused>(log2b, hipErrorInvalidValue, f);
+}
 
 hipError_t launch_process(int log2b, const ProcArgs &a, int channels, hipStream_t s) {
     if (channels <= 0) return hipSuccess;
     if (log2b > kMaxLog2Fused) return launch_process_large(log2b, a, a.lg, a.lg_chunks, channels, s);
-    FFTCONV_DISPATCH(launch_process_t, log2b, a, channels, s)
+    return dispatch_fused(log2b, [&](auto L) { return launch_process_t<L()>(a, channels, s); });
 }
 
 // Lookahead geometry policy: block sizes whose row is whole waves of float4
@@ -2806,7 +2717,7 @@ hipError_t launch_process(int log2b, const ProcArgs &a, int channels, hipStream_
 // function of (B, S) only, never of the channel count.
 int la_parts(int log2b, int S) {
     if (log2b < 7 || log2b > 9) return 0;
-    if (g_variant != VARIANT_AUTO && (g_variant & VARIANT_NOLA)) return 0;
+    if (Variant::current().has(VARIANT_NOLA)) return 0;
     if (S < 40) return 0;  // (channels whose active segments drop below D0 + 2 step generically)
     return 1;
 }
@@ -2868,8 +2779,8 @@ static hipError_t launch_la_t(const ProcArgs &a, int channels, hipStream_t s) {
             return hipErrorInvalidValue;
         // the full-pass streams: nontemporal once the whole H + FDL working
         // set exceeds the Infinity Cache
-        const double stream = 16.0 * (double)channels * (double)a.job[0].S * (double)(1 << LOG2B);
-        const bool ntl = !scan_variant_set() ? stream > 192.0 * 1024 * 1024 : (g_variant & VARIANT_NT) != 0;
+        const Variant v = Variant::current();
+        const bool ntl = v.nt_stream(Variant::stream_bytes(channels, a.job[0].S, LOG2B));
         auto kern = a.la_mix == 1   ? (ntl ? upols_la_kernel<LOG2B, true, 1> : upols_la_kernel<LOG2B, false, 1>)
                     : a.la_mix == 2 ? (ntl ? upols_la_kernel<LOG2B, true, 2> : upols_la_kernel<LOG2B, false, 2>)
                     : xf3           ? (ntl ? upols_la_kernel<LOG2B, true, 3> : upols_la_kernel<LOG2B, false, 3>)
@@ -2881,7 +2792,7 @@ static hipError_t launch_la_t(const ProcArgs &a, int channels, hipStream_t s) {
         args.la_c0 = 0;
         args.la_rebuild = 0;
         args.la_t = a.la_t % LA_PER;
-        if (g_variant != VARIANT_AUTO && (g_variant & VARIANT_LAFULL)) args.la_all = -1;  // no anchors: every eligible step sums all its rows
+        if (v.has(VARIANT_LAFULL)) args.la_all = -1;  // no anchors: every eligible step sums all its rows
         // standalone batches at B <= 256: level 1 in the level-2 anchor
         // workgroups (they finish their walks first); the crossfade launches
         // keep it in the step workgroups (LaStep::MIDIN)
@@ -2889,23 +2800,18 @@ static hipError_t launch_la_t(const ProcArgs &a, int channels, hipStream_t s) {
         const bool midin = !fold && LOG2B <= LA_MIDIN_MAXLOG;
         la_counts(args, LOG2B, a.job[0].S, channels, args.la_all > 0, !fold && !midin, fold);
         if (args.la_all < 0) args.la_n[0] = args.la_n[1] = args.la_n[2] = 0;
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
         const int nstep = (channels + nch - 1) / nch;
         if (a.la_mix == 2 && a.job[0].add0) return hipErrorInvalidValue;  // (the fused mix uses the add buffers' LDS)
         const int xwg = a.la_mix == 1 ? LA_XWG : 0;  // A's launch: the mix_value walk workgroups
         const int nanch = (xf3 ? 2 : 1) * (args.la_n[0] + args.la_n[1] + args.la_n[2]);
-        hipLaunchKernelGGL(kern, dim3(nanch + nstep + xwg), dim3(LA_NT), lds, s, args);
-        return hipGetLastError();
+        return launch_dyn(kern, dim3(nanch + nstep + xwg), dim3(LA_NT), lds, s, args);
     }
 }
 
 hipError_t launch_process_la(int log2b, const ProcArgs &a, int channels, hipStream_t s) {
     if (channels <= 0) return hipSuccess;
     if (a.njobs != (a.la_mix == 3 ? 2 : 1) || !a.laW) return hipErrorInvalidValue;
-    FFTCONV_DISPATCH(launch_la_t, log2b, a, channels, s)
+    return dispatch_fused(log2b, [&](auto L) { return launch_la_t<L()>(a, channels, s); });
 }
 
 int la_trace_grid(int log2b, int S, int channels) {  // (steady-state launches: la_t = 0 has the most anchors)
@@ -2974,8 +2880,7 @@ static hipError_t launch_rebuild_t(const ProcArgs &a, int channels, hipStream_t 
         constexpr size_t anchor_bytes = (size_t)(LA_NG - 1) * RB_JW * LG::FS * 16;  // (LaGeo::anchor_bytes at RB_JW)
         constexpr size_t lds = (anchor_bytes + 15) / 16 * 16 + 16;
         if (!a.laW || a.njobs != 1 || a.job[0].n != (1 << LOG2B)) return hipErrorInvalidValue;
-        const double stream = 16.0 * (double)channels * (double)a.job[0].S * (double)(1 << LOG2B);
-        const bool ntl = !scan_variant_set() ? stream > 192.0 * 1024 * 1024 : (g_variant & VARIANT_NT) != 0;
+        const bool ntl = Variant::current().nt_stream(Variant::stream_bytes(channels, a.job[0].S, LOG2B));
         auto kern = ntl ? la_rebuild_kernel<LOG2B, true> : la_rebuild_kernel<LOG2B, false>;
         ProcArgs args = a;
         args.la_channels = channels;
@@ -2986,50 +2891,41 @@ static hipError_t launch_rebuild_t(const ProcArgs &a, int channels, hipStream_t 
         const int nch = channels - a.la_c0;
         if (nch <= 0) return hipSuccess;
         la_counts(args, LOG2B, a.job[0].S, channels, true, true, false, RB_JW);  // (level 1 in workgroups of its own)
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kern, dim3(args.la_n[0] + args.la_n[1] + args.la_n[2]), dim3(LA_NT), lds, s, args);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        hipLaunchKernelGGL(la_rebuild_state_kernel<LOG2B>, dim3((nch + 255) / 256), dim3(256), 0, s, args);
-        return hipGetLastError();
+        if (hipError_t e = launch_dyn(kern, dim3(args.la_n[0] + args.la_n[1] + args.la_n[2]), dim3(LA_NT), lds, s, args);
+            e != hipSuccess)
+            return e;
+        return launch_dyn(la_rebuild_state_kernel<LOG2B>, dim3((nch + 255) / 256), dim3(256), 0, s, args);
     }
 }
 
 hipError_t launch_la_rebuild(int log2b, const ProcArgs &a, int channels, hipStream_t s) {
     if (channels <= 0) return hipSuccess;
-    FFTCONV_DISPATCH(launch_rebuild_t, log2b, a, channels, s)
+    return dispatch_fused(log2b, [&](auto L) { return launch_rebuild_t<L()>(a, channels, s); });
 }
-
-bool la_full_variant() { return g_variant != VARIANT_AUTO && (g_variant & VARIANT_LAFULL); }
 
 hipError_t launch_ir_segments(int log2b, const IrArgs &a, int channels, hipStream_t s) {
     if (channels <= 0 || a.S <= 0) return hipSuccess;
-    FFTCONV_DISPATCH(launch_ir_t, log2b, a, channels, s)
+    return dispatch_fused(log2b, [&](auto L) { return launch_ir_t<L()>(a, channels, s); });
 }
 
 hipError_t launch_fft_rows(int log2m, bool inverse, const FftArgs &a, int rows, hipStream_t s) {
     if (rows <= 0) return hipSuccess;
-    FFTCONV_DISPATCH(launch_fft_t, log2m, inverse, a, rows, s)
+    return dispatch_fused(log2m, [&](auto L) { return launch_fft_t<L()>(inverse, a, rows, s); });
 }
 
 hipError_t launch_twostage_accum(const TwoStageAccumArgs &a, int channels, hipStream_t s) {
     if (channels <= 0 || a.cnt <= 0) return hipSuccess;
-    hipLaunchKernelGGL(twostage_accum_kernel, dim3(channels), dim3(a.cnt >= 256 ? 256 : 64), 0, s, a);
-    return hipGetLastError();
+    return launch_dyn(twostage_accum_kernel, dim3(channels), dim3(a.cnt >= 256 ? 256 : 64), 0, s, a);
 }
 
 hipError_t launch_crossfade_mix(const CrossfadeMixArgs &a, int channels, hipStream_t s) {
     if (channels <= 0 || a.n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(crossfade_mix_kernel, dim3(channels), dim3(256), 0, s, a);
-    return hipGetLastError();
+    return launch_dyn(crossfade_mix_kernel, dim3(channels), dim3(256), 0, s, a);
 }
 
 hipError_t launch_crossfade_walk(const CrossfadeMixArgs &a, float *vtab, hipStream_t s) {
     if (a.n <= 0 || !a.approaching) return hipSuccess;
-    hipLaunchKernelGGL(crossfade_walk_kernel, dim3(1), dim3(64), 0, s, a, vtab);
-    return hipGetLastError();
+    return launch_dyn(crossfade_walk_kernel, dim3(1), dim3(64), 0, s, a, vtab);
 }
 
 template <int LOG2B>
@@ -3039,19 +2935,13 @@ static hipError_t launch_pair_t(const ProcArgs &a, int channels, hipStream_t s) 
     } else {
         constexpr int PNT = proc_nt(LOG2B);
         using PG = PairGeo<LOG2B, PNT>;
-        const int var = pick_variant(a, channels, LOG2B);
+        const int var = pick_variant(Variant::current(), a, channels, LOG2B);
         if (var & (VARIANT_ZIGZAG | VARIANT_NOPAIR)) return hipErrorNotSupported;  // the pair scan is the plain order only
         ProcArgs args = a;
         args.pipe = 0;
         args.lag = 0;
         auto kern = (var & VARIANT_NT) ? upols_pair_kernel<LOG2B, PNT, true> : upols_pair_kernel<LOG2B, PNT, false>;
-        if (PG::lds_bytes > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)PG::lds_bytes);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kern, dim3(channels), dim3(PNT), PG::lds_bytes, s, args);
-        return hipGetLastError();
+        return launch_dyn(kern, dim3(channels), dim3(PNT), PG::lds_bytes, s, args);
     }
 }
 
@@ -3060,13 +2950,13 @@ bool pair_supported(int log2b, int S) {
     // a quarter of the bytes; short ones are latency-bound and run better as
     // two pipelined workgroups
     return log2b >= 1 && log2b <= 9 && ((long long)S << log2b) > 16384 &&
-           (g_variant == VARIANT_AUTO || !(g_variant & (VARIANT_ZIGZAG | VARIANT_NOPAIR)));
+           !Variant::current().has(VARIANT_ZIGZAG | VARIANT_NOPAIR);
 }
 
 hipError_t launch_process_pair(int log2b, const ProcArgs &a, int channels, hipStream_t s) {
     if (channels <= 0) return hipSuccess;
     if (a.njobs != 2) return hipErrorInvalidValue;
-    FFTCONV_DISPATCH(launch_pair_t, log2b, a, channels, s)
+    return dispatch_fused(log2b, [&](auto L) { return launch_pair_t<L()>(a, channels, s); });
 }
 
 __global__ void state_flags_kernel(int4 *state, int channels, int set, int clear) {
@@ -3076,32 +2966,17 @@ __global__ void state_flags_kernel(int4 *state, int channels, int set, int clear
 
 hipError_t launch_state_flags(int4 *state, int channels, int set, int clear, hipStream_t s) {
     if (channels <= 0) return hipSuccess;
-    hipLaunchKernelGGL(state_flags_kernel, dim3((channels + 255) / 256), dim3(256), 0, s, state, channels, set, clear);
-    return hipGetLastError();
+    return launch_dyn(state_flags_kernel, dim3((channels + 255) / 256), dim3(256), 0, s, state, channels, set, clear);
 }
-
-void set_variant(int v) { g_variant = v < 0 ? VARIANT_AUTO : (v & 4095); }
-bool gw_windows_allowed() { return g_variant == VARIANT_AUTO || !(g_variant & VARIANT_NOGW); }
-bool tail0_defer_allowed() { return g_variant == VARIANT_AUTO || !(g_variant & VARIANT_T0BLOCK); }
-bool la_fuse_mix_allowed() { return g_variant == VARIANT_AUTO || !(g_variant & VARIANT_NOFMIX); }
-void set_pipeline_lag(int rows) { g_lag = rows < 0 ? -1 : rows; }
-int get_pipeline_lag() { return g_lag; }
-int get_variant() { return g_variant == VARIANT_AUTO ? -1 : g_variant; }
 
 hipError_t launch_reset_state(int4 *state, int channels, hipStream_t s) {
     if (channels <= 0) return hipSuccess;
-    hipLaunchKernelGGL(reset_state_kernel, dim3((channels + 255) / 256), dim3(256), 0, s, state, channels);
-    return hipGetLastError();
+    return launch_dyn(reset_state_kernel, dim3((channels + 255) / 256), dim3(256), 0, s, state, channels);
 }
 
 size_t process_lds_bytes(int log2b) {
-    switch (log2b) {
-#define LDSCASE(L) case L: return Geo<L, proc_nt(L)>::lds_bytes;
-        LDSCASE(0) LDSCASE(1) LDSCASE(2) LDSCASE(3) LDSCASE(4) LDSCASE(5) LDSCASE(6)
-        LDSCASE(7) LDSCASE(8) LDSCASE(9) LDSCASE(10) LDSCASE(11) LDSCASE(12) LDSCASE(13)
-#undef LDSCASE
-        default: return 0;
-    }
+    return dispatch_log2<0, kMaxLog2Fused>(log2b, (size_t)0,
+                                           [](auto L) -> size_t { return Geo<L(), proc_nt(L())>::lds_bytes; });
 }
 
 }  // namespace fftconv

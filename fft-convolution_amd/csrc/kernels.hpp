@@ -3,13 +3,15 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include "variant.hpp"
+
 // FFTCONV_DEBUG_BOUNDS (debug builds only, Makefile target debug-bounds):
 // DBG_CHECK(cond, site, v0..v3) reports a failed index check with printf.
 // One out-of-line report per translation unit (a printf inlined at each of
 // the hundreds of inlined load sites made the debug build compile for hours).
 #ifdef FFTCONV_DEBUG_BOUNDS
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
-static __device__ __attribute__((noinline)) void dbg_bounds(int site, int v0, int v1, int v2, int v3) {
+static __device__ __attribute__((noinline, unused)) void dbg_bounds(int site, int v0, int v1, int v2, int v3) {
     printf("BOUNDS site %d blk %d tid %d: %d %d %d %d\n", site, (int)blockIdx.x, (int)threadIdx.x, v0, v1, v2, v3);
 }
 #endif
@@ -56,24 +58,6 @@ enum : int {
     LA_MASK = FLAG_LA1 | FLAG_LA2 | FLAG_LA3 | FLAG_NEAR | FLAG_GW,
     SEQ_MASK = 3 << SEQ_SHIFT,
 };
-
-// fused-kernel variants (bit mask): 1 = zig-zag segment scan, 2 = nontemporal H/X loads
-enum : int {
-    VARIANT_ZIGZAG = 1, VARIANT_NT = 2, VARIANT_NOPIPE = 4, VARIANT_NOPAIR = 8, VARIANT_NOLA = 16,
-    VARIANT_LAFULL = 32,  // lookahead launches without anchors: every step sums all rows itself (tests)
-    VARIANT_NOFMIX = 64,  // crossfade on the lookahead step: stand-alone mix kernel instead of B's epilogue
-    VARIANT_IRBLOCK = 128,  // IR transforms: one segment per workgroup (else one per wave, 64 <= B <= 1024)
-    VARIANT_T0BLOCK = 256,  // two-stage: tail0 per block (else deferred to the end of its period), read at create
-    VARIANT_T0FUSED = 512,  // deferred tail0 at B = 64: the five-kernel flush instead of the fused one (bit-identical)
-    VARIANT_NOGW = 1024,    // B >= 1024: no far-row windows, every step sums its far rows itself (tests)
-    VARIANT_NORUN = 2048,   // process_device_steps: one launch per call (else a run of a period's calls per launch)
-    VARIANT_NORUNLDS = 4096,  // runs stream the FDL / IR rows from memory (else from LDS copies when they fit; same bits)
-    VARIANT_AUTO = 0x7fffffff
-};
-void set_variant(int v);
-int get_variant();
-void set_pipeline_lag(int rows);
-int get_pipeline_lag();
 
 // One convolver batch's call (FFTConvolver::process over `n` samples of every
 // channel), optionally with the two-stage epilogue of the head block
@@ -290,7 +274,6 @@ hipError_t launch_process_run(int log2b, const ProcArgs &a, const RunSteps &r, i
 hipError_t launch_ir_segments(int log2b, const IrArgs &a, int channels, hipStream_t s);
 hipError_t launch_twostage_accum(const TwoStageAccumArgs &a, int channels, hipStream_t s);
 hipError_t launch_crossfade_mix(const CrossfadeMixArgs &a, int channels, hipStream_t s);
-bool la_fuse_mix_allowed();  // VARIANT_NOFMIX unset
 hipError_t launch_reset_state(int4 *state, int channels, hipStream_t s);
 // crossfade pair (A and B of one CrossfadeConvolver in one workgroup per channel)
 bool pair_supported(int log2b, int S);
@@ -316,7 +299,6 @@ hipError_t launch_process_la(int log2b, const ProcArgs &a, int channels, hipStre
 // every far and mid window of channels [a.la_c0, channels) rebuilt from the
 // current H and FDL (anchors only), then their state words pointed at them
 hipError_t launch_la_rebuild(int log2b, const ProcArgs &a, int channels, hipStream_t s);
-bool la_full_variant();  // VARIANT_LAFULL: lookahead launches without anchors
 
 // Two-stage tail0 deferred to the end of its period (src/fft_convolver.rs
 // :464-475: tail_output0 is first read after the period's swap).  pa.job[0]
@@ -339,7 +321,6 @@ struct Tail0Args {
     int *miss;             // [C]: 1 = the run missed some of this channel's spectra: recompute [0, n) (ProcJob::t0m)
 };
 bool tail0_defer_supported(int log2b, int act, int nmax);
-bool tail0_defer_allowed();  // VARIANT_T0BLOCK unset
 // done (optional): an event recorded by the flush's last kernel itself (hipExtLaunchKernel)
 hipError_t launch_tail0_flush(int log2b, const Tail0Args &a, int channels, hipStream_t s, hipEvent_t done = nullptr);
 
@@ -353,7 +334,6 @@ constexpr int kGwP = 8;
 // a batch of this geometry sums far rows through windows: 1024 <= B <= 8192
 // and enough far rows to pay for the anchors
 bool gw_supported(int log2b, int S);
-bool gw_windows_allowed();  // VARIANT_NOGW unset
 // the windows of the channels of class a.gw_t mod kGwP, from the state after
 // the step just launched (a.job[0]: H, X, state, S; a.la_channels channels)
 hipError_t launch_gw_anchor(int log2b, const ProcArgs &a, int channels, hipStream_t s);
@@ -399,8 +379,7 @@ struct MatrixArgs {
     int P;                 // MAC parts (matrix_mac_parts)
     int rpp;               // rows per part = ceil(I * (act - 1) / P)
     int cur, act, fill, k;
-    int nt_h;              // nontemporal loads of the H stream (H larger than the Infinity Cache; with a
-                           // kernel variant set, its VARIANT_NT bit instead -- same bits either way)
+    int nt_h;              // nontemporal loads of the H stream (Variant::nt_matrix; same bits either way)
 };
 // P for a geometry and its active segments: a function of these only
 int matrix_mac_parts(int inputs, int log2b, int seg_count, int active);

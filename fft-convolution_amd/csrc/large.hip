@@ -40,6 +40,7 @@
 
 #include "fft_lds.hpp"
 #include "kernels.hpp"
+#include "launch.hpp"
 
 namespace fftconv {
 namespace {
@@ -758,13 +759,6 @@ __global__ __launch_bounds__(256) void lg_update_state(IrArgs a, int B, int acti
     }
 }
 
-template <class K>
-hipError_t lds_attr(K kern, size_t lds) {
-    if (lds > 64 * 1024)
-        return hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    return hipSuccess;
-}
-
 template <int LM>
 hipError_t lg_process_t(const ProcArgs &a, const LgTab &t, int chunks, int channels, hipStream_t s) {
     using G = LgGeo<LM>;
@@ -1021,11 +1015,9 @@ template <int LP>
 hipError_t bs_launch_t(const BsPass &p0, int rows, int batch, hipStream_t s) {
     if constexpr (LP <= 13) {
         constexpr size_t lds = 2 * ((size_t)1 << LP) * sizeof(float2);
-        if (hipError_t e = lds_attr(bs_small<LP>, lds); e != hipSuccess) return e;
         BsPass p = p0;
         p.row0 = 0;
-        hipLaunchKernelGGL(bs_small<LP>, dim3(rows), dim3(LG_NT), lds, s, p);
-        return hipGetLastError();
+        return launch_dyn(bs_small<LP>, dim3(rows), dim3(LG_NT), lds, s, p);
     } else {
         using G = LgGeo<LP>;
         for (int r0 = 0; r0 < rows; r0 += batch) {
@@ -1043,19 +1035,11 @@ hipError_t bs_launch_t(const BsPass &p0, int rows, int batch, hipStream_t s) {
 
 }  // namespace
 
-#define LG_DISPATCH(FN, LM, ...)                     \
-    switch (LM) {                                    \
-        case 14: return FN<14>(__VA_ARGS__);         \
-        case 15: return FN<15>(__VA_ARGS__);         \
-        case 16: return FN<16>(__VA_ARGS__);         \
-        case 17: return FN<17>(__VA_ARGS__);         \
-        case 18: return FN<18>(__VA_ARGS__);         \
-        case 19: return FN<19>(__VA_ARGS__);         \
-        case 20: return FN<20>(__VA_ARGS__);         \
-        case 21: return FN<21>(__VA_ARGS__);         \
-        case 22: return FN<22>(__VA_ARGS__);         \
-        default: return hipErrorInvalidValue;        \
-    }
+// the long blocks: 2^14 <= B <= 2^22
+template <class F>
+static hipError_t dispatch_large(int log2b, F &&f) {
+    return dispatch_log2<kMaxLog2Fused + 1, kMaxLog2Block>(log2b, hipErrorInvalidValue, f);
+}
 
 void lg_split(int log2b, int *l1, int *l2) {
     *l2 = log2b - 6 < 11 ? log2b - 6 : 11;
@@ -1072,18 +1056,18 @@ size_t lg_position(int log2b, size_t k) {
 hipError_t launch_process_large(int log2b, const ProcArgs &a, const LgTab &t, int chunks, int channels,
                                 hipStream_t s) {
     if (channels <= 0) return hipSuccess;
-    LG_DISPATCH(lg_process_t, log2b, a, t, chunks, channels, s)
+    return dispatch_large(log2b, [&](auto L) { return lg_process_t<L()>(a, t, chunks, channels, s); });
 }
 
 hipError_t launch_ir_large(int log2b, const IrArgs &a, const LgTab &t, int channels, hipStream_t s) {
     if (channels <= 0 || a.S <= 0) return hipSuccess;
-    LG_DISPATCH(lg_ir_t, log2b, a, t, channels, s)
+    return dispatch_large(log2b, [&](auto L) { return lg_ir_t<L()>(a, t, channels, s); });
 }
 
 hipError_t launch_fft_large(int log2m, bool inverse, const FftArgs &a, const LgTab &t, float2 *scratch, int rows,
                             int batch, hipStream_t s) {
     if (rows <= 0) return hipSuccess;
-    LG_DISPATCH(lg_fft_t, log2m, inverse, a, t, scratch, rows, batch, s)
+    return dispatch_large(log2m, [&](auto L) { return lg_fft_t<L()>(inverse, a, t, scratch, rows, batch, s); });
 }
 
 hipError_t launch_fft_bluestein(size_t n, int log2p, bool inverse, const FftArgs &a, const float2 *chirp,
@@ -1104,13 +1088,8 @@ hipError_t launch_fft_bluestein(size_t n, int log2p, bool inverse, const FftArgs
     p.twP = twP;
     p.tb = t;
     p.Y = scratch;
-    switch (log2p) {
-#define BSC(L) case L: return bs_launch_t<L>(p, rows, batch, s);
-        BSC(1) BSC(2) BSC(3) BSC(4) BSC(5) BSC(6) BSC(7) BSC(8) BSC(9) BSC(10) BSC(11) BSC(12) BSC(13)
-        BSC(14) BSC(15) BSC(16) BSC(17) BSC(18) BSC(19) BSC(20) BSC(21) BSC(22)
-#undef BSC
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_log2<1, kMaxLog2Block>(log2p, hipErrorInvalidValue,
+                                           [&](auto L) { return bs_launch_t<L()>(p, rows, batch, s); });
 }
 
 }  // namespace fftconv

@@ -22,6 +22,7 @@
 
 #include "fft_lds.hpp"
 #include "kernels.hpp"
+#include "launch.hpp"
 
 namespace fftconv {
 namespace {
@@ -308,18 +309,9 @@ hipError_t launch_matrix_t(const MatrixArgs &a, hipStream_t s) {
     using Gm = MGeo<LOG2B, NT>;
     auto ka = a.nt_h ? matrix_a_kernel<LOG2B, NT, true> : matrix_a_kernel<LOG2B, NT, false>;
     auto kb = matrix_b_kernel<LOG2B, NT>;
-    if (Gm::lds_a > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)ka, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Gm::lds_a);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void *)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Gm::lds_b);
-        if (e != hipSuccess) return e;
-    }
     const long long grid = (long long)a.I + (a.fill == 0 ? (long long)a.O * a.P : 0);
-    hipLaunchKernelGGL(ka, dim3((unsigned)grid), dim3(NT), Gm::lds_a, s, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kb, dim3(a.O), dim3(NT), Gm::lds_b, s, a);
-    return hipGetLastError();
+    if (hipError_t e = launch_dyn(ka, dim3((unsigned)grid), dim3(NT), Gm::lds_a, s, a); e != hipSuccess) return e;
+    return launch_dyn(kb, dim3(a.O), dim3(NT), Gm::lds_b, s, a);
 }
 
 }  // namespace
@@ -340,18 +332,8 @@ hipError_t launch_matrix_chunk(int log2b, const MatrixArgs &a, hipStream_t s) {
         a.cur < 0 || a.cur >= a.S || a.act > a.S)
         return hipErrorInvalidValue;
     if ((long long)a.I + (long long)a.O * a.P > (long long)INT32_MAX) return hipErrorInvalidValue;
-    switch (log2b) {
-        case 5: return launch_matrix_t<5>(a, s);
-        case 6: return launch_matrix_t<6>(a, s);
-        case 7: return launch_matrix_t<7>(a, s);
-        case 8: return launch_matrix_t<8>(a, s);
-        case 9: return launch_matrix_t<9>(a, s);
-        case 10: return launch_matrix_t<10>(a, s);
-        case 11: return launch_matrix_t<11>(a, s);
-        case 12: return launch_matrix_t<12>(a, s);
-        case 13: return launch_matrix_t<13>(a, s);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_log2<5, kMaxLog2Fused>(log2b, hipErrorInvalidValue,
+                                           [&](auto L) { return launch_matrix_t<L()>(a, s); });
 }
 
 }  // namespace fftconv

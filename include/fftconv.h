@@ -122,14 +122,17 @@ int fftconv_fft_inverse_host(int device, size_t n, size_t rows, const float *inp
  * wave for 64 <= B <= 1024; bit-identical), bit 8 = two-stage tail0 runs
  * per head block (by default its blocks are convolved together at the end
  * of each tail period; read when a TwoStageFFTConvolver is created), bit 9 =
- * that end-of-period flush in one fused kernel instead of five (head block
- * 64; bit-identical), bit 10 = no far-row windows for B >= 1024 (every
+ * that end-of-period flush in five kernels instead of the one fused kernel
+ * that is the default (head block 64; bit-identical), bit 10 = no far-row windows for B >= 1024 (every
  * one-block call sums its far rows itself; bit-identical), bit 11 =
  * process_device_steps launches once per call (by default, for 64 <= B <= 512,
  * a TwoStageFFTConvolver's aligned calls inside one tail period, and the
  * calls of an FFTConvolver batch on the generic / pipelined step with at most
  * two channels per CU, run as ONE launch in which each channel's workgroup
  * loops over its calls; bit-identical).
+ * The table above the VARIANT_ enum in fft-convolution_amd/csrc/variant.hpp
+ * has one row per bit, and says which are read per launch and which when a
+ * handle is created.
  * Lookahead (automatic for standalone FFTConvolver batches with
  * 128 <= B <= 512 and >= 40 segments, full-block calls from an empty input
  * buffer): the FDL sum of each block is re-associated in time over a near
