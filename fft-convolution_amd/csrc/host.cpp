@@ -2297,6 +2297,23 @@ T *make_or_null(int r, T *p) {
 
 }  // namespace
 
+// The process-wide tuning knobs (variant.hpp; like g_stage_limit above, but
+// read by the launchers of every kernel file).  Relaxed atomics: set / read
+// from any thread; a launcher reads each once.
+namespace fftconv {
+static std::atomic<int> g_variant{VARIANT_AUTO};
+static std::atomic<int> g_lag{-1};
+
+void set_variant(int v) { g_variant.store(v < 0 ? VARIANT_AUTO : (v & 4095), std::memory_order_relaxed); }
+Variant Variant::current() { return Variant{g_variant.load(std::memory_order_relaxed)}; }
+int get_variant() {
+    const Variant v = Variant::current();
+    return v.is_auto() ? -1 : v.bits;
+}
+void set_pipeline_lag(int rows) { g_lag.store(rows < 0 ? -1 : rows, std::memory_order_relaxed); }
+int get_pipeline_lag() { return g_lag.load(std::memory_order_relaxed); }
+}  // namespace fftconv
+
 // ===========================================================================
 // C ABI
 // A caller's stream argument: NULL is HIP's null (legacy default) stream, as

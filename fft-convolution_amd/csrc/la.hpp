@@ -1,6 +1,6 @@
 // la.hpp -- lookahead step: FFTConvolver::process with the FDL sum
-// re-associated in time (included by kernels.hip, inside namespace fftconv,
-// after its helpers).
+// re-associated in time.  Device code of upols_la_kernel and of the window
+// rebuild, plus the level constants their launchers read (lookahead.hip).
 //
 // The reference computes, for every block s of a channel (src/fft_convolver.rs
 // :244-261),
@@ -47,7 +47,15 @@
 // VARIANT_LAFULL) give the same bits: results do not depend on the stagger,
 // the channel index or the shard size.
 #pragma once
-// (no namespace of its own: included inside namespace fftconv)
+#include <hip/hip_runtime.h>
+
+#include "fft_lds.hpp"
+#include "kernels.hpp"
+#include "mix.hpp"  // (B's lookahead launch can fuse the crossfade mix)
+#include "packed.hpp"
+#include "step.hpp"
+
+namespace fftconv {
 
 constexpr int LA_D0 = 4;                     // near rows 1..D0, summed by the step
 constexpr int LA_P1 = 4, LA_R1 = 16;         // level 1: rows D0+1..R1, period P1
@@ -88,36 +96,6 @@ __host__ __device__ constexpr int la_flag_live(int lv) { return FLAG_LA1 << (2 *
 __host__ __device__ constexpr int la_flag_win(int lv) { return FLAG_PW1 << (2 * (lv - 1)); }
 // anchor levels of a geometry: level 3 only when some FDL row reaches it
 __host__ __device__ constexpr int la_nlv(int S) { return S > LA_R2 + 1 ? 3 : 2; }
-
-typedef float f2v __attribute__((ext_vector_type(2)));
-
-// Per-row operands of one float4 slot (2 bins).  Bin 0 of slot 0 is the packed
-// (DC, Nyquist) pair, multiplied component-wise; operand selection makes the
-// same two packed FMAs do both (q0 = 0 adds a signed zero there).
-struct LaH {
-    f2v p0, q0, p1, q1;
-};
-__device__ __forceinline__ LaH la_ops(float4 h, bool z0) {
-    LaH o;
-    o.p0 = f2v{h.x, z0 ? h.y : h.x};
-    o.q0 = z0 ? f2v{0.f, 0.f} : f2v{-h.y, h.y};
-    o.p1 = f2v{h.z, h.z};
-    o.q1 = f2v{-h.w, h.w};
-    return o;
-}
-// complex_multiply_accumulate (src/fft_convolver.rs:62-74) over 2 bins:
-// re = fma(-h.im, x.im, fma(h.re, x.re, re)), im = fma(h.im, x.re, fma(h.re, x.im, im))
-struct LaAcc {
-    f2v a01, a23;
-    __device__ __forceinline__ void zero() { a01 = f2v{0.f, 0.f}; a23 = f2v{0.f, 0.f}; }
-    __device__ __forceinline__ void mac(const LaH &h, float4 x) {
-        a01 = __builtin_elementwise_fma(h.p0, f2v{x.x, x.y}, a01);
-        a01 = __builtin_elementwise_fma(h.q0, f2v{x.y, x.x}, a01);
-        a23 = __builtin_elementwise_fma(h.p1, f2v{x.z, x.w}, a23);
-        a23 = __builtin_elementwise_fma(h.q1, f2v{x.w, x.z}, a23);
-    }
-    __device__ __forceinline__ float4 get() const { return make_float4(a01.x, a01.y, a23.x, a23.y); }
-};
 
 __device__ __forceinline__ bool la_live(int w, int lv) { return (w & la_flag_live(lv)) != 0; }
 
@@ -938,7 +916,7 @@ __device__ __forceinline__ void la_step(const ProcArgs &a, const ProcJob &J, con
 // response) in the workgroup: its channels run one at a time, out of line
 // (the rare fallback keeps its registers out of the step's allocation)
 template <int LOG2B, bool NTL, int XF>
-__device__ __attribute__((noinline)) void la_fallback(const ProcArgs *ap, int c0, int nvalid, unsigned char *smem) {
+static __device__ __attribute__((noinline)) void la_fallback(const ProcArgs *ap, int c0, int nvalid, unsigned char *smem) {
     const ProcArgs &a = *ap;
     const ProcJob &J = a.job[0];
     for (int k = 0; k < nvalid; ++k) {
@@ -1008,7 +986,7 @@ __device__ __attribute__((noinline)) void la_fallback(const ProcArgs *ap, int c0
 // generic step (out to buf_a / buf_b), then the workgroup walks mix_value and
 // mixes (the same arithmetic as the lookahead mix)
 template <int LOG2B, bool NTL>
-__device__ __attribute__((noinline)) void la_fallback_xf(const ProcArgs *ap, int c, unsigned char *smem) {
+static __device__ __attribute__((noinline)) void la_fallback_xf(const ProcArgs *ap, int c, unsigned char *smem) {
     const ProcArgs &a = *ap;
     const CrossfadeMixArgs m = a.mix;
     ProcJob Ja = a.job[0], Jb = a.job[1];
@@ -1052,7 +1030,7 @@ constexpr int LA_XWG = 8;  // A's launch: leading workgroups (the first writes t
 // entry it has reached -- the reference's sequential f32 additions, one lane,
 // into LDS -- so B's epilogue reads one word per sample and no crossfader
 // state.  (Out of line: keeps its registers out of the step's allocation.)
-__device__ __attribute__((noinline)) void la_mix_walk(const ProcArgs *ap, unsigned char *smem) {
+static __device__ __attribute__((noinline)) void la_mix_walk(const ProcArgs *ap, unsigned char *smem) {
     // (the walk's operands in registers: stores through the LDS pointer could
     // otherwise alias the kernel arguments and reload them every entry)
     const CrossfadeMixArgs m = ap->mix;
@@ -1215,3 +1193,5 @@ __global__ __launch_bounds__(LA_NT, 4) void upols_la_kernel(ProcArgs a) {
         }
     }
 }
+
+}  // namespace fftconv

@@ -41,6 +41,7 @@
 #include "fft_lds.hpp"
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "packed.hpp"
 
 namespace fftconv {
 namespace {
@@ -145,30 +146,12 @@ __device__ __forceinline__ float2 *bfft(float2 *src, float2 *dst, const float2 *
     }
 }
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ntload(const float4 *p) {  // streaming read: H / FDL rows are used once per block
-    const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-
-__device__ __forceinline__ bool finite2(float2 v) { return isfinite(v.x) && isfinite(v.y); }
-
 // complex_multiply_accumulate (:62-74) on a pair of positions; position 0 is
-// the packed (DC, Nyquist) slot (two real products)
+// the packed (DC, Nyquist) slot.  slot_mac with h in its first multiplicand:
+// term for term the FMAs this path has always issued (fmaf(h, x, acc)).
 __device__ __forceinline__ float4 mac4(float4 acc, float4 h, float4 x, bool slot0) {
-    float4 r;
-    if (slot0) {
-        r.x = fmaf(h.x, x.x, acc.x);
-        r.y = fmaf(h.y, x.y, acc.y);
-    } else {
-        r.x = fmaf(-h.y, x.y, fmaf(h.x, x.x, acc.x));
-        r.y = fmaf(h.y, x.x, fmaf(h.x, x.y, acc.y));
-    }
-    r.z = fmaf(-h.w, x.w, fmaf(h.z, x.z, acc.z));
-    r.w = fmaf(h.w, x.z, fmaf(h.z, x.w, acc.w));
-    return r;
+    return slot_mac(acc, h, x, slot0 ? 0 : 1);
 }
-__device__ __forceinline__ float4 vadd4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
 // one channel's chunk of the reference's chunk loop (:222-232), from its
 // block state and the call's progress word {processed, done, c2r failed,
@@ -221,7 +204,7 @@ struct LgPass {
 };
 
 // the far-row split of a channel's pre_multiplied (0 = one sum) and whether
-// this chunk reads its window row: the generic step's rule (kernels.hip
+// this chunk reads its window row: the generic step's rule (step.hpp
 // process_job) -- a one-block call from an empty input buffer, window live
 __device__ __forceinline__ int lg_split(const LgPass &p, const Chunk &ch) {
     return p.gw_p > 0 && ch.act > p.gw_p ? p.gw_p : 0;
@@ -447,8 +430,8 @@ __global__ __launch_bounds__(LG_NT) void lg_rows(LgPass p) {
                         for (int u = 0; u < EP; ++u) {
                             DBG_CHECK(xr >= 0 && xr < ch.act && 2 * q[u] + 1 < (size_t)M, 54, xr, ch.act, (int)q[u],
                                       i + t);  // (site 54: a MAC row)
-                            hv[t][u] = ntload(H4 + (size_t)(i + t) * RF + q[u]);
-                            xv[t][u] = ntload(X4 + (size_t)xr * RF + q[u]);
+                            hv[t][u] = ntld4(H4 + (size_t)(i + t) * RF + q[u]);
+                            xv[t][u] = ntld4(X4 + (size_t)xr * RF + q[u]);
                         }
                         if (++xr == ch.act) xr = 0;
                     }
@@ -464,8 +447,8 @@ __global__ __launch_bounds__(LG_NT) void lg_rows(LgPass p) {
 #pragma unroll
                     for (int u = 0; u < EP; ++u) {
                         DBG_CHECK(xi >= 0 && xi < ch.act, 54, xi, ch.act, (int)q[u], i);
-                        hv[u] = ntload(H4 + (size_t)i * RF + q[u]);
-                        xv[u] = ntload(X4 + (size_t)xi * RF + q[u]);
+                        hv[u] = ntld4(H4 + (size_t)i * RF + q[u]);
+                        xv[u] = ntld4(X4 + (size_t)xi * RF + q[u]);
                     }
 #pragma unroll
                     for (int u = 0; u < EP; ++u) r[u] = mac4(r[u], hv[u], xv[u], tid == 0 && u == 0 && rp.w == 0);
@@ -484,12 +467,12 @@ __global__ __launch_bounds__(LG_NT) void lg_rows(LgPass p) {
                 DBG_CHECK(k >= 0 && k < sp, 60, k, p.gw_t, sp, (int)row);  // (site 60: the window row)
                 const float4 *wr = reinterpret_cast<const float4 *>(p.gw + (row * sp + k) * (size_t)M);
 #pragma unroll
-                for (int u = 0; u < EP; ++u) acc[u] = vadd4(acc[u], ntload(wr + q[u]));
+                for (int u = 0; u < EP; ++u) acc[u] = vadd(acc[u], ntld4(wr + q[u]));
             } else if (sp) {
                 float4 far[EP];
                 mac_range(far, sp, ch.act);
 #pragma unroll
-                for (int u = 0; u < EP; ++u) acc[u] = vadd4(acc[u], far[u]);
+                for (int u = 0; u < EP; ++u) acc[u] = vadd(acc[u], far[u]);
             }
 #pragma unroll
             for (int u = 0; u < EP; ++u)
@@ -517,11 +500,11 @@ __global__ __launch_bounds__(LG_NT) void lg_rows(LgPass p) {
                 // operand rows' (DC, Nyquist) parts is not finite, while a
                 // finite overflow leaves it 0 (and runs the C2R on inf).  A
                 // carried pre_multiplied was summed from the same rows.
-                bool bad = !finite2(make_float2(x.x, x.y)) || !finite2(make_float2(h0.x, h0.y));
-                if (!bad && !finite2(make_float2(acc[0].x, acc[0].y))) {
+                bool bad = !slot0_finite(make_float2(x.x, x.y)) || !slot0_finite(make_float2(h0.x, h0.y));
+                if (!bad && !slot0_finite(make_float2(acc[0].x, acc[0].y))) {
                     for (int i = 1; i < ch.act && !bad; ++i) {
                         const int xi = (ch.cur + i) % ch.act;
-                        bad = !finite2(Hc[(size_t)i * M]) || !finite2(Xc[(size_t)xi * M]);
+                        bad = !slot0_finite(Hc[(size_t)i * M]) || !slot0_finite(Xc[(size_t)xi * M]);
                     }
                 }
                 if (bad) reinterpret_cast<int *>(J.lg_prog + row)[2] = 1;

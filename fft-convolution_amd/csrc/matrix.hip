@@ -23,56 +23,10 @@
 #include "fft_lds.hpp"
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "packed.hpp"
 
 namespace fftconv {
 namespace {
-
-typedef float mf32x4 __attribute__((ext_vector_type(4)));
-template <bool NTL>
-__device__ __forceinline__ float4 mld4(const float4 *p) {
-    if constexpr (NTL) {
-        const mf32x4 v = __builtin_nontemporal_load(reinterpret_cast<const mf32x4 *>(p));
-        return make_float4(v.x, v.y, v.z, v.w);
-    } else {
-        return *p;
-    }
-}
-__device__ __forceinline__ float4 madd4(float4 a, float4 b) {
-    return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-}
-
-// complex_multiply_accumulate (src/fft_convolver.rs:62-74) over one 16-byte
-// slot (2 bins); dc / ny carry the products of the packed real bins so that
-// slot 0 resolves as (DC, Nyquist).  The uniform path's accumulator.
-struct MAcc {
-    float4 a;
-    float dc, ny;
-    __device__ __forceinline__ void zero() { a = make_float4(0.f, 0.f, 0.f, 0.f); dc = ny = 0.f; }
-    __device__ __forceinline__ void mac(float4 h, float4 x) {
-        a.x = fmaf(-h.y, x.y, fmaf(h.x, x.x, a.x));
-        a.y = fmaf(h.y, x.x, fmaf(h.x, x.y, a.y));
-        a.z = fmaf(-h.w, x.w, fmaf(h.z, x.z, a.z));
-        a.w = fmaf(h.w, x.z, fmaf(h.z, x.w, a.w));
-        dc = fmaf(h.x, x.x, dc);
-        ny = fmaf(h.y, x.y, ny);
-    }
-    __device__ __forceinline__ float4 get(int slot) const { return slot == 0 ? make_float4(dc, ny, a.z, a.w) : a; }
-};
-
-// conv = pre + x (.) h for one slot, packed-aware
-__device__ __forceinline__ float4 mslot_mac(float4 pre, float4 x, float4 h, int slot) {
-    float4 r;
-    if (slot == 0) {
-        r.x = fmaf(x.x, h.x, pre.x);
-        r.y = fmaf(x.y, h.y, pre.y);
-    } else {
-        r.x = fmaf(-x.y, h.y, fmaf(x.x, h.x, pre.x));
-        r.y = fmaf(x.y, h.x, fmaf(x.x, h.y, pre.y));
-    }
-    r.z = fmaf(-x.w, h.w, fmaf(x.z, h.z, pre.z));
-    r.w = fmaf(x.w, h.z, fmaf(x.z, h.w, pre.w));
-    return r;
-}
 
 // (tests/matrix_paths.py mirrors these constants, matrix_nt, UB and the P rule
 // to prove which loops each test shape runs: change them together)
@@ -148,7 +102,7 @@ __device__ __forceinline__ void matrix_mac(const MatrixArgs &a, int o, int p, un
     const float4 *H4 = reinterpret_cast<const float4 *>(a.H) + (size_t)o * a.I * a.S * F;
     const float4 *X4 = reinterpret_cast<const float4 *>(a.X);
 
-    MAcc acc[SPT];
+    Acc2 acc[SPT];
 #pragma unroll
     for (int s = 0; s < SPT; ++s) acc[s].zero();
     long long r = r0 + g;
@@ -181,8 +135,8 @@ __device__ __forceinline__ void matrix_mac(const MatrixArgs &a, int o, int p, un
             const float4 *hp = hrow(), *xp = xrow();
 #pragma unroll
             for (int q = 0; q < SPT; ++q) {
-                hv[u][q] = mld4<NTL>(hp + q * NT);
-                xv[u][q] = mld4<false>(xp + q * NT);
+                hv[u][q] = ld4<NTL>(hp + q * NT);
+                xv[u][q] = ld4<false>(xp + q * NT);
             }
             advance();
         }
@@ -194,7 +148,7 @@ __device__ __forceinline__ void matrix_mac(const MatrixArgs &a, int o, int p, un
     while (r < r1) {
         const float4 *hp = hrow(), *xp = xrow();
 #pragma unroll
-        for (int q = 0; q < SPT; ++q) acc[q].mac(mld4<NTL>(hp + q * NT), mld4<false>(xp + q * NT));
+        for (int q = 0; q < SPT; ++q) acc[q].mac(ld4<NTL>(hp + q * NT), ld4<false>(xp + q * NT));
         advance();
     }
 
@@ -206,7 +160,7 @@ __device__ __forceinline__ void matrix_mac(const MatrixArgs &a, int o, int p, un
         if (tid < F) {
             float4 v = red[f0];
 #pragma unroll
-            for (int q = 1; q < G; ++q) v = madd4(v, red[q * F + f0]);
+            for (int q = 1; q < G; ++q) v = vadd(v, red[q * F + f0]);
             dst[f0] = v;
         }
     } else {
@@ -266,7 +220,7 @@ __global__ __launch_bounds__(NT) void matrix_b_kernel(MatrixArgs a) {
                         if (p + u < a.P) t[u] = part4[(size_t)(p + u) * F + f];
 #pragma unroll
                     for (int u = 0; u < UB; ++u)
-                        if (p + u < a.P) v = p + u == 0 ? t[u] : madd4(v, t[u]);
+                        if (p + u < a.P) v = p + u == 0 ? t[u] : vadd(v, t[u]);
                 }
             } else {
                 v = pre4[f];
@@ -283,7 +237,7 @@ __global__ __launch_bounds__(NT) void matrix_b_kernel(MatrixArgs a) {
                 }
 #pragma unroll
                 for (int u = 0; u < UB / 2; ++u)
-                    if (i + u < a.I) v = mslot_mac(v, xs[u], hs[u], f);
+                    if (i + u < a.I) v = slot_mac(v, xs[u], hs[u], f);
             }
             reinterpret_cast<float4 *>(bufA)[f] = v;
         }

@@ -46,7 +46,7 @@ int get_pipeline_lag();
 struct Variant {
     int bits;  // VARIANT_AUTO, or the bits set
 
-    static Variant current();  // (one relaxed load, kernels.hip)
+    static Variant current();  // (one relaxed load, host.cpp)
 
     bool is_auto() const { return bits == VARIANT_AUTO; }
     bool has(int bit) const { return !is_auto() && (bits & bit) != 0; }

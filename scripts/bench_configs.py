@@ -50,7 +50,7 @@ def uniform_bytes(B, L):
 
 
 def tail0_deferred_bytes_per_block(head, T):
-    """tail0 deferred to the period end (csrc/kernels.hip tail0_*_kernel), per
+    """tail0 deferred to the period end (csrc/tail0.hip tail0_*_kernel), per
     channel and head block, in rows of 8*head bytes: over a period of n = T/head
     blocks the flush reads the S0 = T/head IR rows and S0-1 FDL rows once, and
     per block writes / reads its spectrum (R2C, MAC, commit: 4 rows incl. the
@@ -64,7 +64,7 @@ GW_P = 8  # far-row windows' split row (csrc/kernels.hpp kGwP)
 
 def windowed_bytes(B, L, P=GW_P):
     """The generic step with far-row windows (1024 <= B <= 8192, DESIGN §4f;
-    csrc/kernels.hip gw_anchor_kernel), per channel-block, in rows of 8 B bytes
+    csrc/process.hip gw_anchor_kernel), per channel-block, in rows of 8 B bytes
     (B packed complex slots, Nyquist in slot 0's imaginary part):
       step: H[1..P-1] and their P-1 FDL rows, the window row, H[0], the new
             FDL row (2P + 1 rows) + input, output, overlap read / write (16 B);

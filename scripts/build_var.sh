@@ -2,8 +2,9 @@
 # Build the working tree's libfftconv_amd.so with a sed patch applied to the
 # kernels into build/var/NAME/ (for same-process or back-to-back A/B).
 #   scripts/build_var.sh NAME 'sed-expression' [file]
+# file: relative to fft-convolution_amd/ (default: csrc/lookahead.hip)
 set -eu
-name=$1; expr=$2; file=${3:-csrc/kernels.hip}
+name=$1; expr=$2; file=${3:-csrc/lookahead.hip}
 root=$(cd "$(dirname "$0")/.." && pwd)
 dst=$root/build/var/$name
 rm -rf "$dst" && mkdir -p "$dst"

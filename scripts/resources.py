@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
-"""Per-kernel VGPR/SGPR/spill/occupancy table from hipcc -Rpass-analysis output."""
+"""Per-kernel VGPR/SGPR/spill/occupancy table from hipcc -Rpass-analysis output.
+
+  scripts/resources.py [file.hip] [kernel-name filter]   (default: csrc/lookahead.hip)
+"""
 import re
 import subprocess
 import sys
 
-src = sys.argv[1] if len(sys.argv) > 1 else "fft-convolution_amd/csrc/kernels.hip"
+src = sys.argv[1] if len(sys.argv) > 1 else "fft-convolution_amd/csrc/lookahead.hip"
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
 out = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-c", src, "-o",
                       "/tmp/_res.o", "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True).stderr

@@ -1,4 +1,4 @@
-"""Two-stage tail0 deferred to the end of its period (csrc/kernels.hip
+"""Two-stage tail0 deferred to the end of its period (csrc/tail0.hip
 tail0_*_kernel; TwoStageFFTConvolver::process, src/fft_convolver.rs:464-475:
 tail_output0 is first read after the period's swap, so the period's head
 blocks are convolved by tail_convolver0 in one pass).  Checked against the

@@ -1,5 +1,5 @@
 """Far-row windows of the generic step (1024 <= B <= 8192, >= 24 segments;
-csrc/kernels.hip gw_anchor_kernel) and of the long-block path
+csrc/process.hip gw_anchor_kernel) and of the long-block path
 (2^14 <= B <= 2^22, csrc/large.hip lg_rows: the same windows, transposed bin
 order).
 
