@@ -1824,12 +1824,13 @@ struct MatrixCore {
     DevPtr<float2> H, X, pre, part, tw;
     DevPtr<float> ovl, ib, staging;
     hipStream_t stream = nullptr;
+    bool own_stream = true;  // false: a MatrixCrossfadeCore's convolver on its owner's stream
     Scratch scratch;
     PinnedStage hstage;
     mutable StreamOrder order;
 
     ~MatrixCore() {
-        if (stream) {
+        if (stream && own_stream) {
             DeviceGuard g(device);
             (void)order.drain(stream);
             (void)hipStreamDestroy(stream);
@@ -2001,14 +2002,20 @@ struct MatrixCore {
         return FFTCONV_OK;
     }
 
-    // #[derive(Clone)]
-    int clone_from(const MatrixCore &o) {
+    // #[derive(Clone)]; `owner`: the clone is a MatrixCrossfadeCore's convolver
+    // -- it runs on that stream and stages updates through its owner
+    int clone_from(const MatrixCore &o, hipStream_t owner = nullptr) {
         DeviceGuard g(o.device);
         if (int r = o.order.drain(o.stream)) return r;
         device = o.device;
         I = o.I; O = o.O; ir_len = o.ir_len; B = o.B; log2b = o.log2b; S = o.S; Pmax = o.Pmax;
         cur = o.cur; act = o.act; fill = o.fill;
-        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        if (owner) {
+            stream = owner;
+            own_stream = false;
+        } else {
+            HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        }
         auto cp = [&](auto &dst, const auto &src) -> int {
             if (int r = dst.alloc(src.n)) return r;
             if (src.n) HIP_TRY(hipMemcpyAsync(dst.p, src.p, src.bytes(), hipMemcpyDeviceToDevice, stream));
@@ -2022,7 +2029,296 @@ struct MatrixCore {
         if (int r = cp(ib, o.ib)) return r;
         if (int r = part.alloc(o.part.n)) return r;  // (rewritten by every block before it is read)
         if (int r = staging.alloc(o.staging.n)) return r;
-        if (int r = hstage.alloc(o.hstage.n, ir_len)) return r;
+        if (!owner)
+            if (int r = hstage.alloc(o.hstage.n, ir_len)) return r;
+        HIP_TRY(hipStreamSynchronize(stream));
+        return FFTCONV_OK;
+    }
+};
+
+// ---------------------------------------------------------------------------
+// MatrixCrossfadeCore -- I x O CrossfadeConvolver<FFTConvolver> instances
+// (o, i) in lockstep: two MatrixCores A and B on the handle's
+// stream, ONE Crossfader and one response_pending for all of them, the mix
+// applied to the per-output sums.
+//   composition path: A.process_device -> buf_a, B.process_device -> buf_b,
+//       crossfade_mix_kernel over the O outputs (always correct)
+//   fused path (matrix_xf.hip), while A and B are in step: one R2C per input
+//       for both delay lines, the live convolvers' MAC from one X stream, the
+//       finish of each live convolver and the mix in one launch.  A convolver
+//       the crossfader has Reached away from is idle: its output is never
+//       observed and the next thing that happens to it is update(), which
+//       zeroes its pre_multiplied and overlap (src/fft_convolver.rs:186-188),
+//       so it carries only its delay line and input buffer forward.
+// ---------------------------------------------------------------------------
+struct MatrixCrossfadeCore {
+    int device = 0;
+    size_t I = 0, O = 0, max_buffer_size = 0, stored_len = 0, stored_stride = 0;
+    size_t stage_row = 0;  // hstage row: the stored response, or a direct update of a / b
+    std::unique_ptr<MatrixCore> a, b;
+    Crossfader xf;
+    DevPtr<float> buf_a, buf_b, stored;  // stored [O*I][stored_len]
+    DevPtr<float> mix_tab;               // [max_buffer_size + 1] mix_value walk of one call
+    bool response_pending = false;
+    // A and B have had equal {current, active, fill} and active > 0 at every
+    // call since creation: their delay lines and input buffers are equal row
+    // for row.  Sticky off (an update to another ceil(len / B) ends it for good).
+    bool in_step = false;
+    bool fused = true;  // fftconv_matrix_crossfade_set_fused
+    // a launch failed between the two convolvers' work: they may be out of
+    // step with the host's state.  Every later call fails.
+    bool poisoned = false;
+    hipStream_t stream = nullptr;
+    Scratch scratch;
+    mutable StreamOrder order;
+    PinnedStage hstage;
+
+    int check_poisoned() const {
+        return poisoned ? fail(FFTCONV_E_DEVICE, "matrix crossfade handle unusable: an earlier process() failed "
+                                                  "between its two convolvers' launches")
+                        : FFTCONV_OK;
+    }
+
+    ~MatrixCrossfadeCore() {
+        if (stream) {
+            DeviceGuard g(device);
+            (void)order.drain(stream);
+            a.reset(); b.reset();  // (they borrow `stream`)
+            (void)hipStreamDestroy(stream);
+        }
+    }
+
+    bool states_agree() const {
+        return a->cur == b->cur && a->act == b->act && a->fill == b->fill && a->act > 0;
+    }
+
+    int alloc_buffers(size_t hstage_count) {
+        if (int r = stored.alloc(O * I * stored_len)) return r;
+        if (int r = hstage.alloc(hstage_count, stage_row)) return r;
+        if (int r = buf_a.alloc(O * max_buffer_size)) return r;
+        if (int r = buf_b.alloc(O * max_buffer_size)) return r;
+        return mix_tab.alloc(max_buffer_size + 1);
+    }
+
+    // CrossfadeConvolver::new (:19-43)
+    int init_new(const MatrixCore &conv, size_t max_response_length, size_t mbs, size_t crossfade_samples) {
+        if (mbs > (size_t)INT32_MAX) return fail(FFTCONV_E_UNSUPPORTED, "max_buffer_size exceeds 2^31-1");
+        device = conv.device;
+        I = conv.I;
+        O = conv.O;
+        DeviceGuard g(device);
+        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        a.reset(new (std::nothrow) MatrixCore());
+        b.reset(new (std::nothrow) MatrixCore());
+        if (!a || !b) return fail(FFTCONV_E_NOMEM, "out of host memory");
+        if (int r = a->clone_from(conv, stream)) return r;
+        if (int r = b->clone_from(conv, stream)) return r;
+        in_step = states_agree();
+        stored_len = max_response_length;
+        stored_stride = stored_len;
+        stage_row = std::max(stored_len, a->ir_len);
+        max_buffer_size = mbs;
+        if (int r = alloc_buffers(O * I * stage_row)) return r;
+        if (stored.n) HIP_TRY(hipMemsetAsync(stored.p, 0, stored.bytes(), stream));
+        xf.init(crossfade_samples, std::min(mbs, max_response_length));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return FFTCONV_OK;
+    }
+
+    int quiesce() const { return order.drain(stream); }
+    bool is_crossfading() const { return xf.approaching; }  // :85-92
+
+    // swap (:94-105) from device samples: update the convolver that is not the
+    // target, then fade into it
+    int swap_device(const float *src, size_t stride, size_t len, hipStream_t s) {
+        const int to = xf.target == 0 ? 1 : 0;
+        if (int r = (to ? *b : *a).update_device(src, stride, len, s)) return r;
+        xf.fade_into(to);
+        return FFTCONV_OK;
+    }
+
+    // Convolution::update (:51-64) from host samples (pair p at src + p * stride,
+    // stride 0 = one response for every pair); staged in pinned memory and
+    // enqueued behind the handle's work: no allocation, no host wait
+    int update_host(const float *src, size_t len, size_t stride) {
+        if (int r = check_poisoned()) return r;
+        DeviceGuard g(device);
+        const bool shared = stride == 0 && O * I > 1;
+        const size_t rows = shared ? 1 : O * I;
+        if (!is_crossfading()) {
+            MatrixCore &t = xf.target == 0 ? *b : *a;
+            if (len > t.ir_len) return fail(FFTCONV_E_INVALID, "New impulse response is longer than initialized length");
+            if (int r = order.enter(stream)) return r;
+            if (len)
+                if (int r = hstage.upload(src, rows, len, stride, t.staging.p, t.ir_len, stream)) return r;
+            if (int r = swap_device(t.staging.p, shared ? 0 : t.ir_len, len, stream)) return r;
+            response_pending = false;
+            return FFTCONV_OK;
+        }
+        if (len > stored_len) return fail(FFTCONV_E_INVALID, "assertion failed: response_len <= self.stored_response.len()");
+        if (int r = order.enter(stream)) return r;
+        // stored_response[..len] = response; stored_response[len..] = 0
+        if (stored.n) HIP_TRY(hipMemsetAsync(stored.p, 0, stored.bytes(), stream));
+        if (len)
+            if (int r = hstage.upload(src, rows, len, stride, stored.p, stored_len, stream)) return r;
+        stored_stride = shared ? 0 : stored_len;
+        response_pending = true;
+        return FFTCONV_OK;
+    }
+
+    // Convolution::update (:51-64) from device samples, stream-ordered (the
+    // caller has ordered s behind the handle's previous work)
+    int update_device(const float *src, size_t len, size_t stride, hipStream_t s) {
+        if (int r = check_poisoned()) return r;
+        if (!is_crossfading()) {
+            if (int r = swap_device(src, stride, len, s)) return r;
+            response_pending = false;
+            return FFTCONV_OK;
+        }
+        if (len > stored_len) return fail(FFTCONV_E_INVALID, "assertion failed: response_len <= self.stored_response.len()");
+        const bool shared = stride == 0 && O * I > 1;
+        if (stored.n) HIP_TRY(hipMemsetAsync(stored.p, 0, stored.bytes(), s));
+        if (len)
+            HIP_TRY(hipMemcpy2DAsync(stored.p, stored_len * sizeof(float), src, (shared ? len : std::max(stride, len)) * sizeof(float),
+                                     len * sizeof(float), shared ? 1 : O * I, hipMemcpyDeviceToDevice, s));
+        stored_stride = shared ? 0 : stored_len;
+        response_pending = true;
+        return FFTCONV_OK;
+    }
+
+    CrossfadeMixArgs mix_args(float *dout, size_t os, size_t out_len) const {
+        CrossfadeMixArgs x{};
+        x.buf_a = buf_a.p; x.buf_b = buf_b.p; x.buf_stride = (long long)max_buffer_size;
+        x.out = dout; x.out_stride = (long long)os; x.n = (int)out_len;
+        x.approaching = xf.approaching ? 1 : 0; x.target = xf.target;
+        x.counter0 = xf.counter; x.fading = xf.fading_samples;
+        x.mix_value0 = xf.mix_value; x.step = xf.mix_value_step;
+        return x;
+    }
+
+    // 0 = composition, 1 = fused with both convolvers live, 2 = fused with one
+    // idle: a function of the handle's state only
+    int path_now() const {
+        if (!fused || !in_step || !states_agree()) return 0;
+        return xf.approaching ? 1 : 2;
+    }
+    // the path the next process() takes: a pending swap is applied first
+    int path_next() const {
+        if (!is_crossfading() && response_pending) {
+            const MatrixCore &t = xf.target == 0 ? *b : *a, &other = xf.target == 0 ? *a : *b;
+            if (t.ir_len == 0 || stored_len > t.ir_len) return path_now();  // (the update changes nothing)
+            const size_t act = ceil_div(stored_len, t.B);
+            return fused && in_step && act > 0 && act == other.act && t.cur == other.cur && t.fill == other.fill ? 1 : 0;
+        }
+        return path_now();
+    }
+
+    // Convolution::process (:66-78): both convolvers advance by max_buffer_size
+    // samples, the first out_len mixed samples are written
+    int process_device(const float *din, size_t is, float *dout, size_t os, size_t out_len, hipStream_t s) {
+        if (int r = check_poisoned()) return r;
+        if (out_len > max_buffer_size) return fail(FFTCONV_E_INVALID, "output longer than max_buffer_size (index out of bounds)");
+        if (!is_crossfading() && response_pending) {                    // :67-70
+            if (int r = swap_device(stored.p, stored_stride, stored_len, s)) return r;
+            response_pending = false;
+        }
+        const size_t m = max_buffer_size;
+        if (m == 0) return FFTCONV_OK;
+        in_step = in_step && states_agree();
+        CrossfadeMixArgs mx = mix_args(dout, os, out_len);
+        if (path_now() == 0) {
+            if (int r = a->process_device(din, is, buf_a.p, m, m, s)) return r;    // :72
+            if (int r = b->process_device(din, is, buf_b.p, m, m, s)) {            // :73
+                poisoned = true;
+                return r;
+            }
+            if (out_len > 1024 && mx.approaching) {
+                HIP_TRY(launch_crossfade_walk(mx, mix_tab.p, s));
+                mx.vtab = mix_tab.p;
+            }
+            HIP_TRY(launch_crossfade_mix(mx, (int)O, s));                          // :75-77
+            xf.advance(out_len);
+            return FFTCONV_OK;
+        }
+        if (mx.approaching) mx.vtab = mix_tab.p;  // the call's mix_value walk: launch A of the first chunk fills it
+        MatrixXfArgs x{};
+        const MatrixCore *cv[2] = {a.get(), b.get()};
+        for (int c = 0; c < 2; ++c) {
+            x.H[c] = cv[c]->H.p; x.X[c] = cv[c]->X.p; x.ovl[c] = cv[c]->ovl.p; x.ib[c] = cv[c]->ib.p;
+            x.pre[c] = cv[c]->pre.p; x.part[c] = cv[c]->part.p;
+        }
+        x.tw = a->tw.p;
+        x.in_stride = (long long)is;
+        x.out_stride = (long long)os;
+        x.I = (int)I; x.O = (int)O; x.S = (int)a->S;
+        x.P = a->mac_parts();
+        x.rpp = (int)ceil_div(I * (a->act - 1), (size_t)x.P);
+        x.act = (int)a->act;
+        x.nt_h = Variant::current().nt_matrix(a->H.bytes()) ? 1 : 0;
+        x.live = xf.approaching ? 3 : (xf.target == 0 ? 1 : 2);
+        x.mix = mx;
+        const size_t B = a->B;
+        size_t processed = 0;
+        while (processed < m) {                                         // FFTConvolver::process :222-294, A and B at once
+            const size_t k = std::min(m - processed, B - a->fill);
+            x.in = din + processed;
+            x.out = dout + processed;
+            x.cur = (int)a->cur;
+            x.fill = (int)a->fill;
+            x.k = (int)k;
+            x.off = (int)processed;
+            x.walk = processed == 0 && mx.approaching ? mix_tab.p : nullptr;
+            if (hipError_t e = launch_matrix_xf_chunk(a->log2b, x, s); e != hipSuccess) {
+                poisoned = true;
+                HIP_TRY(e);
+            }
+            a->fill += k;
+            if (a->fill == B) {
+                a->fill = 0;
+                a->cur = a->cur > 0 ? a->cur - 1 : a->act - 1;
+            }
+            b->fill = a->fill;
+            b->cur = a->cur;
+            processed += k;
+        }
+        xf.advance(out_len);
+        return FFTCONV_OK;
+    }
+
+    int process_host(const float *in, size_t in_len, float *out, size_t out_len) {
+        if (in_len < max_buffer_size) return fail(FFTCONV_E_INVALID, "input shorter than max_buffer_size (range end index out of range)");
+        if (out_len > max_buffer_size) return fail(FFTCONV_E_INVALID, "output longer than max_buffer_size (index out of bounds)");
+        if (int r = check_poisoned()) return r;
+        DeviceGuard g(device);
+        if (int r = order.enter(stream)) return r;
+        const size_t m = max_buffer_size, on = std::max<size_t>(out_len, 1);
+        if (int r = scratch.ensure(I * std::max<size_t>(m, 1), O * on)) return r;
+        if (m)
+            HIP_TRY(hipMemcpy2DAsync(scratch.in.p, m * sizeof(float), in, in_len * sizeof(float), m * sizeof(float), I,
+                                     hipMemcpyHostToDevice, stream));
+        if (int r = process_device(scratch.in.p, m, scratch.out.p, on, out_len, stream)) return r;
+        if (out_len && m)
+            HIP_TRY(hipMemcpy2DAsync(out, out_len * sizeof(float), scratch.out.p, on * sizeof(float),
+                                     out_len * sizeof(float), O, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return FFTCONV_OK;
+    }
+
+    int clone_from(const MatrixCrossfadeCore &o) {
+        DeviceGuard g(o.device);
+        if (int r = o.order.drain(o.stream)) return r;
+        device = o.device; I = o.I; O = o.O; max_buffer_size = o.max_buffer_size;
+        stored_len = o.stored_len; stored_stride = o.stored_stride; stage_row = o.stage_row;
+        xf = o.xf; response_pending = o.response_pending;
+        in_step = o.in_step; fused = o.fused; poisoned = o.poisoned;
+        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        a.reset(new (std::nothrow) MatrixCore());
+        b.reset(new (std::nothrow) MatrixCore());
+        if (!a || !b) return fail(FFTCONV_E_NOMEM, "out of host memory");
+        if (int r = a->clone_from(*o.a, stream)) return r;
+        if (int r = b->clone_from(*o.b, stream)) return r;
+        if (int r = alloc_buffers(o.hstage.n)) return r;
+        if (stored.n) HIP_TRY(hipMemcpyAsync(stored.p, o.stored.p, stored.bytes(), hipMemcpyDeviceToDevice, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         return FFTCONV_OK;
     }
@@ -2324,6 +2620,7 @@ struct fftconv_uniform { UniformCore core; };
 struct fftconv_twostage { TwoStageCore core; };
 struct fftconv_crossfade { CrossfadeCore core; };
 struct fftconv_matrix { MatrixCore core; };
+struct fftconv_matrix_crossfade { MatrixCrossfadeCore core; };
 
 extern "C" {
 
@@ -2742,5 +3039,92 @@ int fftconv_matrix_state(const fftconv_matrix *h, size_t out3[3]) {
     out3[0] = h->core.cur; out3[1] = h->core.act; out3[2] = h->core.fill;
     return FFTCONV_OK;
 }
+
+// ---- matrix crossfade ---------------------------------------------
+fftconv_matrix_crossfade *fftconv_matrix_crossfade_init(int device, size_t inputs, size_t outputs,
+                                                        const float *responses, size_t response_len,
+                                                        size_t response_stride, size_t max_block_size,
+                                                        size_t max_response_length) {
+    fftconv_matrix *conv = fftconv_matrix_init(device, inputs, outputs, responses, response_len, response_stride,
+                                               max_block_size, max_response_length);
+    if (!conv) return nullptr;
+    // Convolution::init (src/crossfade_convolver.rs:46-49)
+    fftconv_matrix_crossfade *h = fftconv_matrix_crossfade_new(conv, response_len, max_block_size, response_len);
+    fftconv_matrix_destroy(conv);
+    return h;
+}
+fftconv_matrix_crossfade *fftconv_matrix_crossfade_new(const fftconv_matrix *convolver, size_t max_response_length,
+                                                       size_t max_buffer_size, size_t crossfade_samples) {
+    if (!convolver) { set_error("null handle"); return nullptr; }
+    auto *h = new (std::nothrow) fftconv_matrix_crossfade();
+    if (!h) { set_error("out of host memory"); return nullptr; }
+    return make_or_null(h->core.init_new(convolver->core, max_response_length, max_buffer_size, crossfade_samples), h);
+}
+int fftconv_matrix_crossfade_update(fftconv_matrix_crossfade *h, const float *responses, size_t response_len,
+                                    size_t response_stride) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.update_host(responses, response_len, response_stride);
+}
+int fftconv_matrix_crossfade_update_device(fftconv_matrix_crossfade *h, const float *d_responses, size_t response_len,
+                                           size_t response_stride, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.device);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int r = h->core.order.enter(s)) return r;
+    return h->core.update_device(d_responses, response_len, response_stride, s);
+}
+int fftconv_matrix_crossfade_reset(fftconv_matrix_crossfade *h) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return fail(FFTCONV_E_UNIMPLEMENTED, "not yet implemented (CrossfadeConvolver::reset is todo!())");
+}
+int fftconv_matrix_crossfade_process(fftconv_matrix_crossfade *h, const float *input, size_t input_len, float *output,
+                                     size_t output_len) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.process_host(input, input_len, output, output_len);
+}
+int fftconv_matrix_crossfade_process_device(fftconv_matrix_crossfade *h, const float *d_input, size_t in_stride,
+                                            float *d_output, size_t out_stride, size_t output_len, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.device);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int r = h->core.order.enter(s)) return r;
+    return h->core.process_device(d_input, in_stride, d_output, out_stride, output_len, s);
+}
+int fftconv_matrix_crossfade_process_device_steps(fftconv_matrix_crossfade *h, const float *d_input, size_t in_stride,
+                                                  size_t in_step, float *d_output, size_t out_stride, size_t out_step,
+                                                  size_t output_len, size_t steps, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.device);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int r = h->core.order.enter(s)) return r;
+    for (size_t k = 0; k < steps; ++k)
+        if (int r = h->core.process_device(d_input + k * in_step, in_stride, d_output + k * out_step, out_stride,
+                                           output_len, s))
+            return r;
+    return FFTCONV_OK;
+}
+int fftconv_matrix_crossfade_is_crossfading(const fftconv_matrix_crossfade *h) {
+    return h && h->core.is_crossfading() ? 1 : 0;
+}
+fftconv_matrix_crossfade *fftconv_matrix_crossfade_clone(const fftconv_matrix_crossfade *h) {
+    if (!h) { set_error("null handle"); return nullptr; }
+    auto *c = new (std::nothrow) fftconv_matrix_crossfade();
+    if (!c) { set_error("out of host memory"); return nullptr; }
+    return make_or_null(c->core.clone_from(h->core), c);
+}
+void fftconv_matrix_crossfade_destroy(fftconv_matrix_crossfade *h) { delete h; }
+int fftconv_matrix_crossfade_synchronize(fftconv_matrix_crossfade *h) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.device);
+    return h->core.quiesce();
+}
+size_t fftconv_matrix_crossfade_inputs(const fftconv_matrix_crossfade *h) { return h ? h->core.I : 0; }
+size_t fftconv_matrix_crossfade_outputs(const fftconv_matrix_crossfade *h) { return h ? h->core.O : 0; }
+int fftconv_matrix_crossfade_set_fused(fftconv_matrix_crossfade *h, int on) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    h->core.fused = on != 0;
+    return FFTCONV_OK;
+}
+int fftconv_matrix_crossfade_path(const fftconv_matrix_crossfade *h) { return h ? h->core.path_next() : 0; }
 
 }  // extern "C"

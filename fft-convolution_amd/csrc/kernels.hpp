@@ -387,4 +387,35 @@ int matrix_mac_parts(int inputs, int log2b, int seg_count, int active);
 // split-row MAC when the chunk starts a block, B = the outputs' finish
 hipError_t launch_matrix_chunk(int log2b, const MatrixArgs &a, hipStream_t s);
 
+// MatrixCrossfadeConvolver (matrix_xf.hip): one chunk of the two
+// matrices A and B of a crossfaded handle while they are in step (equal
+// {current, active, fill} at every call since creation, so X[0] and X[1], ib[0]
+// and ib[1] are equal row for row).  [0] = convolver A, [1] = convolver B.
+struct MatrixXfArgs {
+    const float2 *H[2];    // [O][I][S][B] each
+    float2 *X[2];          // [I][S][B] each; the chunk's row is written to both
+    float *ovl[2];         // [O][B]
+    float *ib[2];          // [I][B]; both maintained
+    float2 *pre[2];        // [O][B]
+    float2 *part[2];       // [O][P][B]
+    const float2 *tw;      // W_N^k, k < N = 2B
+    const float *in;       // chunk of input 0 (+ in_stride per input)
+    long long in_stride;
+    float *out;            // chunk of output 0 (+ out_stride per output)
+    long long out_stride;
+    int I, O, S;
+    int P, rpp;            // as MatrixArgs
+    int cur, act, fill, k;
+    int nt_h;              // nontemporal H streams (Variant::nt_matrix of one H)
+    int live;              // bit 0: A, bit 1: B -- an idle convolver (Crossfader Reached the other)
+                           // keeps only its delay line: no MAC, no finish, no C2R
+    int off;               // the chunk's offset in the call (mix sample index = off + j)
+    CrossfadeMixArgs mix;  // the call's crossfader state; n = output_len, vtab = the device walk
+                           // table while approaching (buf_a / buf_b unused)
+    float *walk;           // the call's first chunk while approaching: mix.vtab, which one more
+                           // workgroup of launch A fills (mix.n + 1 entries); null in every other chunk
+};
+// the chunk's two launches (32 <= B <= 8192)
+hipError_t launch_matrix_xf_chunk(int log2b, const MatrixXfArgs &a, hipStream_t s);
+
 }  // namespace fftconv

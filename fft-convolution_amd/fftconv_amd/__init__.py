@@ -118,6 +118,22 @@ SIGNATURES = {
     "fftconv_matrix_seg_count": (_sz, [_vp]),
     "fftconv_matrix_mac_parts": (_i, [_vp]),
     "fftconv_matrix_state": (_i, [_vp, C.POINTER(_sz)]),
+    "fftconv_matrix_crossfade_init": (_vp, [_i, _sz, _sz, _fp, _sz, _sz, _sz, _sz]),
+    "fftconv_matrix_crossfade_new": (_vp, [_vp, _sz, _sz, _sz]),
+    "fftconv_matrix_crossfade_update": (_i, [_vp, _fp, _sz, _sz]),
+    "fftconv_matrix_crossfade_update_device": (_i, [_vp, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_crossfade_reset": (_i, [_vp]),
+    "fftconv_matrix_crossfade_process": (_i, [_vp, _fp, _sz, _fp, _sz]),
+    "fftconv_matrix_crossfade_process_device": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_crossfade_process_device_steps": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _sz, _sz, _vp]),
+    "fftconv_matrix_crossfade_is_crossfading": (_i, [_vp]),
+    "fftconv_matrix_crossfade_clone": (_vp, [_vp]),
+    "fftconv_matrix_crossfade_destroy": (None, [_vp]),
+    "fftconv_matrix_crossfade_synchronize": (_i, [_vp]),
+    "fftconv_matrix_crossfade_inputs": (_sz, [_vp]),
+    "fftconv_matrix_crossfade_outputs": (_sz, [_vp]),
+    "fftconv_matrix_crossfade_set_fused": (_i, [_vp, _i]),
+    "fftconv_matrix_crossfade_path": (_i, [_vp]),
 }
 
 
@@ -586,8 +602,83 @@ class MatrixConvolver(_Base):
         return tuple(int(v) for v in out)
 
 
+class MatrixCrossfadeConvolver(_Base):
+    """Crossfaded response switching for the matrix (fftconv.h,
+    "MatrixCrossfadeConvolver"): inputs x outputs CrossfadeConvolver<FFTConvolver>
+    instances in lockstep, one crossfader, the mix applied to the per-output sums."""
+
+    _prefix = "matrix_crossfade"
+
+    def __init__(self, h, inputs: int, outputs: int, max_buffer_size: int):
+        super().__init__(h, inputs)
+        self.inputs = inputs
+        self.outputs = outputs
+        self.max_buffer_size = max_buffer_size
+
+    @classmethod
+    def init(cls, responses, max_block_size: int, max_response_length: int, device: int = 0):
+        """Convolution::init (:46-49) over responses[O][I][len]: the fade takes
+        len samples, the hold min(max_block_size, len)."""
+        r = MatrixConvolver._pairs(responses)
+        O, I, n = r.shape
+        h = lib().fftconv_matrix_crossfade_init(device, I, O, _p(r), n, n, max_block_size, max_response_length)
+        return cls(_handle(h), I, O, max_block_size)
+
+    @classmethod
+    def new(cls, convolver: MatrixConvolver, max_response_length: int, max_buffer_size: int, crossfade_samples: int):
+        """CrossfadeConvolver::new (:19-43); the MatrixConvolver is cloned."""
+        if not isinstance(convolver, MatrixConvolver):
+            raise TypeError("convolver must be a MatrixConvolver")
+        h = lib().fftconv_matrix_crossfade_new(convolver._h, max_response_length, max_buffer_size, crossfade_samples)
+        return cls(_handle(h), convolver.inputs, convolver.outputs, max_buffer_size)
+
+    def update(self, responses):
+        """update() of every pair with responses[O][I][len] (:51-64): starts the
+        fade, or is stored until the fade under way has ended."""
+        r = MatrixConvolver._pairs(responses, self.inputs, self.outputs)
+        _check(lib().fftconv_matrix_crossfade_update(self._h, _p(r), r.shape[2], r.shape[2]))
+
+    def update_device(self, d_responses: int, response_len: int, stride: int = 0, stream: int = 0):
+        """update() from device memory (pair o * inputs + i at d_responses +
+        4 * pair * stride; stride 0 = one response for every pair), stream-ordered."""
+        _check(self._fn("update_device")(self._h, C.c_void_p(d_responses), response_len, stride,
+                                         C.c_void_p(stream) if stream else None))
+
+    def reset(self):
+        _check(lib().fftconv_matrix_crossfade_reset(self._h))
+
+    def process(self, inp, out_len: int | None = None) -> np.ndarray:
+        """x[inputs][n >= max_buffer_size] -> y[outputs][out_len or n]; the state
+        advances by max_buffer_size samples whatever out_len is."""
+        x = _f32(inp)
+        if x.ndim != 2 or x.shape[0] != self.inputs:
+            raise ValueError(f"input must be [{self.inputs}][n]")
+        n_in = x.shape[1]
+        n = n_in if out_len is None else out_len
+        y = np.zeros((self.outputs, n), np.float32)
+        _check(lib().fftconv_matrix_crossfade_process(self._h, _p(x), n_in, _p(y), n))
+        return y
+
+    def is_crossfading(self) -> bool:
+        return bool(lib().fftconv_matrix_crossfade_is_crossfading(self._h))
+
+    def clone(self):
+        return MatrixCrossfadeConvolver(_handle(lib().fftconv_matrix_crossfade_clone(self._h)), self.inputs,
+                                        self.outputs, self.max_buffer_size)
+
+    def set_fused(self, on: bool):
+        """False: every call takes the composition path (tests, A/B runs)."""
+        _check(lib().fftconv_matrix_crossfade_set_fused(self._h, 1 if on else 0))
+
+    def path(self) -> int:
+        """The path the next process() takes: 0 composition, 1 fused with both
+        convolvers live, 2 fused with one convolver idle."""
+        return int(lib().fftconv_matrix_crossfade_path(self._h))
+
+
 __all__ = [
-    "Fft", "FFTConvolver", "TwoStageFFTConvolver", "CrossfadeConvolver", "MatrixConvolver", "ConvolutionPanic",
+    "Fft", "FFTConvolver", "TwoStageFFTConvolver", "CrossfadeConvolver", "MatrixConvolver",
+    "MatrixCrossfadeConvolver", "ConvolutionPanic",
     "NotImplementedInReference", "DeviceError", "complex_size", "compute_tail_block_size", "device_count",
     "lib", "LIB_PATH", "SIGNATURES",
 ]

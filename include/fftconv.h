@@ -61,6 +61,7 @@ typedef struct fftconv_uniform fftconv_uniform;     /* FFTConvolver        src/f
 typedef struct fftconv_twostage fftconv_twostage;   /* TwoStageFFTConvolver src/fft_convolver.rs:323-512 */
 typedef struct fftconv_crossfade fftconv_crossfade; /* CrossfadeConvolver<FFTConvolver | TwoStageFFTConvolver> src/crossfade_convolver.rs:10-105 */
 typedef struct fftconv_matrix fftconv_matrix;       /* inputs x outputs FFTConvolver instances, summed per output (below) */
+typedef struct fftconv_matrix_crossfade fftconv_matrix_crossfade; /* inputs x outputs CrossfadeConvolver<FFTConvolver> instances (below) */
 
 /* ---- library ----------------------------------------------------------- */
 int fftconv_abi_version(void);
@@ -369,6 +370,86 @@ size_t fftconv_matrix_seg_count(const fftconv_matrix *h);
 int fftconv_matrix_mac_parts(const fftconv_matrix *h);
 /* {current, active_seg_count, input_buffer_fill} as of the calls enqueued so far */
 int fftconv_matrix_state(const fftconv_matrix *h, size_t out3[3]);
+
+/* ---- MatrixCrossfadeConvolver: crossfaded response switching for the matrix ----
+ * A matrix crossfade (inputs I, outputs O) behaves as I*O reference
+ * CrossfadeConvolver<FFTConvolver> instances (o, i) (src/crossfade_convolver.rs:
+ * 3-105), all created and updated together with the same lengths: instance
+ * (o, i) processes input i, output o is the sum over i.  Every instance's
+ * crossfader is in lockstep, so the handle has one Crossfader and one pending
+ * response.  The device mixes the per-output sums, mix(sum_i a, sum_i b), not
+ * the per-instance mixes: equal to the definition within f32 rounding, not
+ * bitwise; in hold and Reached samples the mix returns a or b unchanged.
+ * Mirrored from the reference:
+ *  - new (:19-43): the convolver is cloned into A and B, hold =
+ *    min(max_buffer_size, max_response_length), the stored response has
+ *    max_response_length samples.  init (:46-49) = new(matrix init(...),
+ *    response_len, max_block_size, response_len).
+ *  - update (:51-64): not crossfading -> the idle convolver is updated and the
+ *    fade starts at once; crossfading -> the response is stored (zero-padded)
+ *    and applied by the first process() after the fade; response_len longer
+ *    than the stored length is FFTCONV_E_INVALID, handle unchanged.  No
+ *    allocation, no host wait.
+ *  - process (:66-78): BOTH convolvers advance by max_buffer_size samples
+ *    whatever output_len is; input_len < max_buffer_size or output_len >
+ *    max_buffer_size is FFTCONV_E_INVALID.
+ *  - reset is todo!() (:80-82): FFTCONV_E_UNIMPLEMENTED.
+ * The matrix's departures carry over: non-finite samples are outside the
+ * contract, only whole-matrix updates.  Pairs and strides as fftconv_matrix_*.
+ * Paths (fftconv_matrix_crossfade_path), chosen by the handle's state only --
+ * every path computes the same bits:
+ *   0  composition: A and B as two plain matrices, then the mix kernel.  Taken
+ *      when A and B are not in step, or after set_fused(h, 0).
+ *   1  fused, both convolvers live (a fade is under way): one forward
+ *      transform per input for both delay lines, every delay-line row streamed
+ *      once for both responses, the mix in the finish kernel's epilogue.
+ *   2  fused, one convolver idle (no fade under way): the convolver that is not
+ *      heard keeps only its delay line; its multiply-accumulate, inverse
+ *      transform and overlap are skipped (exact: its next event is update(),
+ *      which zeroes what was skipped, :186-188 of fft_convolver.rs).
+ * A and B are in step while they have had equal {current, active_seg_count,
+ * input_buffer_fill} and active_seg_count > 0 at every call since creation; an
+ * update to another ceil(response_len / block) ends that for good.
+ * Every supported block size (32..8192) runs fused: the finish kernel keeps
+ * A's samples in the output buffer between its two passes and reads the fade
+ * curve from a device table, so it needs no more LDS than the plain matrix. */
+fftconv_matrix_crossfade *fftconv_matrix_crossfade_init(int device, size_t inputs, size_t outputs,
+                                                        const float *responses, size_t response_len,
+                                                        size_t response_stride, size_t max_block_size,
+                                                        size_t max_response_length);
+/* `convolver` is cloned (the caller keeps ownership of its handle). */
+fftconv_matrix_crossfade *fftconv_matrix_crossfade_new(const fftconv_matrix *convolver, size_t max_response_length,
+                                                       size_t max_buffer_size, size_t crossfade_samples);
+int fftconv_matrix_crossfade_update(fftconv_matrix_crossfade *h, const float *responses, size_t response_len,
+                                    size_t response_stride);
+int fftconv_matrix_crossfade_update_device(fftconv_matrix_crossfade *h, const float *d_responses,
+                                           size_t response_len, size_t response_stride, void *hip_stream);
+int fftconv_matrix_crossfade_reset(fftconv_matrix_crossfade *h);
+/* input [inputs][input_len], output [outputs][output_len], host memory. */
+int fftconv_matrix_crossfade_process(fftconv_matrix_crossfade *h, const float *input, size_t input_len,
+                                     float *output, size_t output_len);
+/* device memory, stream-ordered: max_buffer_size samples of input i at d_input +
+ * i * in_stride, output_len samples of output o at d_output + o * out_stride. */
+int fftconv_matrix_crossfade_process_device(fftconv_matrix_crossfade *h, const float *d_input, size_t in_stride,
+                                            float *d_output, size_t out_stride, size_t output_len,
+                                            void *hip_stream);
+/* `steps` consecutive process_device calls; the same bits as the separate calls. */
+int fftconv_matrix_crossfade_process_device_steps(fftconv_matrix_crossfade *h, const float *d_input,
+                                                  size_t in_stride, size_t in_step, float *d_output,
+                                                  size_t out_stride, size_t out_step, size_t output_len,
+                                                  size_t steps, void *hip_stream);
+int fftconv_matrix_crossfade_is_crossfading(const fftconv_matrix_crossfade *h); /* :85-92, 1/0 */
+fftconv_matrix_crossfade *fftconv_matrix_crossfade_clone(const fftconv_matrix_crossfade *h);
+void fftconv_matrix_crossfade_destroy(fftconv_matrix_crossfade *h);
+int fftconv_matrix_crossfade_synchronize(fftconv_matrix_crossfade *h);
+size_t fftconv_matrix_crossfade_inputs(const fftconv_matrix_crossfade *h);
+size_t fftconv_matrix_crossfade_outputs(const fftconv_matrix_crossfade *h);
+/* tests and A/B runs: on = 0 makes every call of this handle take the
+ * composition path (default 1); a clone inherits the setting. */
+int fftconv_matrix_crossfade_set_fused(fftconv_matrix_crossfade *h, int on);
+/* the path (0, 1 or 2 above) the next process() would take, a pending
+ * response included */
+int fftconv_matrix_crossfade_path(const fftconv_matrix_crossfade *h);
 
 #ifdef __cplusplus
 }
