@@ -1824,7 +1824,7 @@ struct MatrixCore {
     DevPtr<float2> H, X, pre, part, tw;
     DevPtr<float> ovl, ib, staging;
     hipStream_t stream = nullptr;
-    bool own_stream = true;  // false: a MatrixCrossfadeCore's convolver on its owner's stream
+    bool own_stream = true;  // false: a MatrixCrossfadeCore's / MatrixTwoStageCore's convolver on its owner's stream
     Scratch scratch;
     PinnedStage hstage;
     mutable StreamOrder order;
@@ -1839,7 +1839,8 @@ struct MatrixCore {
 
     int mac_parts() const { return matrix_mac_parts((int)I, log2b, (int)S, (int)act); }
 
-    int alloc_geometry(int dev, size_t inputs, size_t outputs, size_t max_block_size, size_t max_len) {
+    int alloc_geometry(int dev, size_t inputs, size_t outputs, size_t max_block_size, size_t max_len,
+                       hipStream_t owner = nullptr) {
         device = dev;
         I = inputs;
         O = outputs;
@@ -1854,7 +1855,12 @@ struct MatrixCore {
             return fail(FFTCONV_E_UNSUPPORTED, "geometry exceeds 32-bit indexing");
         act = S;
         Pmax = (size_t)matrix_mac_parts((int)I, log2b, (int)S, (int)S);
-        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        if (owner) {
+            stream = owner;
+            own_stream = false;
+        } else {
+            HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        }
         if (int r = H.alloc(O * I * S * B)) return r;
         if (int r = X.alloc(I * S * B)) return r;
         if (int r = pre.alloc(O * B)) return r;
@@ -1904,15 +1910,16 @@ struct MatrixCore {
         return FFTCONV_OK;
     }
 
+    // `owner`: the matrix is a stage of a MatrixTwoStageCore and runs on that stream
     int init(int dev, size_t inputs, size_t outputs, const float *responses, size_t len, size_t stride,
-             size_t max_block, size_t max_len) {
+             size_t max_block, size_t max_len, hipStream_t owner = nullptr) {
         if (inputs == 0 || outputs == 0) return fail(FFTCONV_E_INVALID, "a matrix needs at least one input and one output");
         if (max_len < len)                                          // :106-110
             return fail(FFTCONV_E_INVALID,
                         "max_response_length must be at least the length of the initial impulse response");
         if (int r = check_device(dev)) return r;
         DeviceGuard g(dev);
-        if (int r = alloc_geometry(dev, inputs, outputs, max_block, max_len)) return r;
+        if (int r = alloc_geometry(dev, inputs, outputs, max_block, max_len, owner)) return r;
         if (int r = zero_state(stream)) return r;
         if (S > 0) {
             const bool shared = stride == 0 && O * I > 1;
@@ -2324,6 +2331,281 @@ struct MatrixCrossfadeCore {
     }
 };
 
+// ---------------------------------------------------------------------------
+// MatrixTwoStageCore -- I x O TwoStageFFTConvolver instances (o, i) in lockstep
+// (DESIGN §4k): up to three MatrixCores (head, tail0, tail) on the handle's
+// stream, ONE {tail_input_fill, precalculated_pos} for all of them, the four
+// tail buffers summed per output [O][T], tail_input per input [I][T].
+//   composition path: TwoStageCore::process_device's sub-chunk loop
+//       (src/fft_convolver.rs:412-495) with matrices for convolvers (always
+//       correct)
+//   fused path (matrix_ts.hip), at an aligned call: head, the sub-chunk's sums
+//       and copy, and tail0 in the plain matrix's two launches, every delay-
+//       line row streamed once for both responses.  Head and tail0 count
+//       samples modulo B from the same start, so at an aligned call their last
+//       S rows are transforms of the same input blocks whatever ragged calls
+//       came before.
+// Everything is enqueued on one stream in stream order; the tail's block-T
+// convolution at the end of a period is enqueued inline, where the reference
+// runs it (:479-486).
+// ---------------------------------------------------------------------------
+struct MatrixTwoStageCore {
+    int device = 0;
+    size_t I = 0, O = 0, head_bs = 0, T = 0;
+    std::unique_ptr<MatrixCore> head, tail0, tail;  // null = the reference's Default convolver (zeros): skipped
+    DevPtr<float> out0, pre0, out1, pre1;           // [O][T] each
+    DevPtr<float> tin;                              // tail_input [I][T]
+    float *tail_output0 = nullptr, *tail_precalculated0 = nullptr;
+    float *tail_output = nullptr, *tail_precalculated = nullptr;
+    size_t tail_input_fill = 0, precalculated_pos = 0;
+    bool fused = true;  // fftconv_matrix_twostage_set_fused
+    // a launch failed inside a call: the stages may be out of step with the
+    // host's scalars.  Every later call fails.
+    bool poisoned = false;
+    hipStream_t stream = nullptr;
+    Scratch scratch;
+    mutable StreamOrder order;
+
+    ~MatrixTwoStageCore() {
+        if (stream) {
+            DeviceGuard g(device);
+            (void)order.drain(stream);
+            head.reset(); tail0.reset(); tail.reset();  // (they borrow `stream`)
+            (void)hipStreamDestroy(stream);
+        }
+    }
+
+    int check_poisoned() const {
+        return poisoned ? fail(FFTCONV_E_DEVICE, "matrix two-stage handle unusable: an earlier process() failed "
+                                                  "between its stages' launches")
+                        : FFTCONV_OK;
+    }
+
+    int alloc_buffers() {
+        for (auto *b : {&out0, &pre0, &out1, &pre1}) {
+            if (int r = b->alloc(O * T)) return r;
+            HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes(), stream));
+        }
+        if (int r = tin.alloc(I * T)) return r;
+        HIP_TRY(hipMemsetAsync(tin.p, 0, tin.bytes(), stream));
+        tail_output0 = out0.p; tail_precalculated0 = pre0.p;
+        tail_output = out1.p; tail_precalculated = pre1.p;
+        return FFTCONV_OK;
+    }
+
+    // TwoStageFFTConvolver::init (:340-406) of every instance
+    int init(int dev, size_t inputs, size_t outputs, const float *responses, size_t len, size_t stride,
+             size_t block_size, size_t max_len) {
+        if (inputs == 0 || outputs == 0) return fail(FFTCONV_E_INVALID, "a matrix needs at least one input and one output");
+        if (max_len < len)                                                      // :344-348
+            return fail(FFTCONV_E_INVALID,
+                        "max_response_length must be at least the length of the initial impulse response");
+        head_bs = block_size;                                                   // :341
+        T = fftconv_compute_tail_block_size(block_size, max_len);              // :342
+        const size_t B = next_pow2(block_size);
+        if (B < 32 || B > 8192)
+            return fail(FFTCONV_E_UNSUPPORTED, "matrix block size " + std::to_string(B) + " outside 32..8192");
+        if (T > 8192)  // (the tail is a matrix of block T)
+            return fail(FFTCONV_E_UNSUPPORTED, "matrix tail block size " + std::to_string(T) + " exceeds 8192");
+        if (inputs > (size_t)INT32_MAX / T || outputs > (size_t)INT32_MAX / T)
+            return fail(FFTCONV_E_UNSUPPORTED, "geometry exceeds 32-bit indexing");
+        if (int r = check_device(dev)) return r;
+        device = dev;
+        I = inputs;
+        O = outputs;
+        DeviceGuard g(dev);
+        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        // padded_ir = each pair's response zero-extended to max_len (:349-350);
+        // the sub-ranges are cut on the host, so each stage sees its reference slice
+        const size_t pairs = O * I;
+        const bool shared = stride == 0 && pairs > 1;
+        std::vector<float> tmp;
+        auto stage = [&](std::unique_ptr<MatrixCore> &m, size_t off, size_t cnt, size_t block) -> int {
+            const size_t rows = shared ? 1 : pairs;
+            tmp.assign(rows * std::max<size_t>(cnt, 1), 0.f);
+            for (size_t p = 0; p < rows; ++p)
+                for (size_t j = 0; j < cnt && off + j < len; ++j) tmp[p * cnt + j] = responses[p * stride + off + j];
+            m.reset(new (std::nothrow) MatrixCore());
+            if (!m) return fail(FFTCONV_E_NOMEM, "out of host memory");
+            return m->init(dev, I, O, tmp.data(), cnt, shared ? 0 : cnt, block, cnt, stream);
+        };
+        if (int r = stage(head, 0, std::min(max_len, T), head_bs)) return r;             // :352-354
+        if (max_len > T)                                                                  // :356-368
+            if (int r = stage(tail0, T, std::min(max_len - T, T), head_bs)) return r;
+        if (max_len > 2 * T)                                                              // :373-384
+            if (int r = stage(tail, 2 * T, max_len - 2 * T, T)) return r;
+        if (int r = alloc_buffers()) return r;
+        HIP_TRY(hipStreamSynchronize(stream));
+        return FFTCONV_OK;
+    }
+
+    // 1 = the next process() of `len` samples takes the fused path: the call
+    // is aligned (a whole power-of-two head block on a block boundary of the
+    // period, both input buffers empty), tail0 exists, and head and tail0 walk
+    // the same rows.  A function of the geometry, the calls so far and `fused`,
+    // never of `outputs`.
+    int path(size_t len) const {
+        if (!fused || !tail0) return 0;
+        const MatrixCore &h = *head, &t = *tail0;
+        return len == head_bs && head_bs == h.B && tail_input_fill % h.B == 0 && tail_input_fill + len <= T &&
+                       h.fill == 0 && t.fill == 0 && h.S == t.S && h.act == t.act && h.act > 0 && h.cur == t.cur
+                   ? 1
+                   : 0;
+    }
+
+    // fill reached T (:473-491): both swaps, then the tail's block-T convolution
+    // of this period, inline
+    int end_of_period(hipStream_t s) {
+        std::swap(tail_precalculated0, tail_output0);                           // :473-475
+        std::swap(tail_precalculated, tail_output);                             // :483
+        if (tail)                                                               // :484-485
+            if (int r = tail->process_device(tin.p, T, tail_output, T, T, s)) return r;
+        tail_input_fill = 0;                                                    // :488-491
+        precalculated_pos = 0;
+        return FFTCONV_OK;
+    }
+
+    int process_composed(const float *din, size_t is, float *dout, size_t os, size_t len, hipStream_t s) {
+        if (int r = head->process_device(din, is, dout, os, len, s)) return r;     // :417
+        size_t processed = 0;
+        while (processed < len) {                                                   // :427
+            const size_t processing = std::min(len - processed, head_bs - (tail_input_fill % head_bs));
+            if (tail_input_fill + processing > T)  // tail_input[fill..fill+processing] out of range (:459-460)
+                return fail(FFTCONV_E_INVALID, "range end index out of range for slice of length tail_block_size");
+            MatrixTsAccumArgs a{};
+            a.out = dout; a.out_stride = (long long)os;
+            a.p0 = tail0 ? tail_precalculated0 : nullptr;
+            a.p1 = tail ? tail_precalculated : nullptr;
+            a.T = (long long)T; a.pos = (int)precalculated_pos;
+            a.in = din; a.in_stride = (long long)is; a.sb = (int)processed;
+            a.tail_input = tin.p; a.fill = (int)tail_input_fill; a.cnt = (int)processing;
+            a.I = (int)I; a.O = (int)O;
+            HIP_TRY(launch_matrix_ts_accum(a, s));                                  // :438-461
+            precalculated_pos += processing;
+            tail_input_fill += processing;
+            if (tail_input_fill % head_bs == 0 && tail0) {                          // :464-472
+                const size_t off = tail_input_fill - head_bs;
+                if (int r = tail0->process_device(tin.p + off, T, tail_output0 + off, T, head_bs, s)) return r;
+            }
+            if (tail_input_fill == T)
+                if (int r = end_of_period(s)) return r;
+            processed += processing;
+        }
+        return FFTCONV_OK;
+    }
+
+    int process_fused(const float *din, size_t is, float *dout, size_t os, hipStream_t s) {
+        MatrixCore &h = *head, &t = *tail0;
+        MatrixTsArgs x{};
+        const MatrixCore *cv[2] = {&h, &t};
+        for (int c = 0; c < 2; ++c) {
+            x.H[c] = cv[c]->H.p; x.X[c] = cv[c]->X.p; x.ovl[c] = cv[c]->ovl.p; x.part[c] = cv[c]->part.p;
+        }
+        x.tw = h.tw.p;
+        x.in = din; x.in_stride = (long long)is;
+        x.out = dout; x.out_stride = (long long)os;
+        x.tin = tin.p + tail_input_fill;                                        // :459-461
+        x.tout0 = tail_output0 + tail_input_fill;                               // :468-472
+        x.p0 = tail_precalculated0 + precalculated_pos;                         // :439-445
+        x.p1 = tail ? tail_precalculated + precalculated_pos : nullptr;         // :448-454
+        x.T = (long long)T;
+        x.I = (int)I; x.O = (int)O; x.S = (int)h.S;
+        x.P = h.mac_parts();
+        x.rpp = (int)ceil_div(I * (h.act - 1), (size_t)x.P);
+        x.cur = (int)h.cur;
+        x.act = (int)h.act;
+        x.nt_h = Variant::current().nt_matrix(h.H.bytes()) ? 1 : 0;
+        HIP_TRY(launch_matrix_ts_block(h.log2b, x, s));
+        h.cur = h.cur > 0 ? h.cur - 1 : h.act - 1;                              // (:277-291 of both)
+        t.cur = h.cur;
+        precalculated_pos += head_bs;
+        tail_input_fill += head_bs;
+        if (tail_input_fill == T) return end_of_period(s);
+        return FFTCONV_OK;
+    }
+
+    // TwoStageFFTConvolver::process (:412-495) of every instance
+    int process_device(const float *din, size_t is, float *dout, size_t os, size_t len, hipStream_t s) {
+        if (int r = check_poisoned()) return r;
+        if (len > head_bs) return fail(FFTCONV_E_INVALID, "assertion failed: input.len() <= self.head_block_size");
+        if (len == 0) return FFTCONV_OK;
+        const int r = path(len) ? process_fused(din, is, dout, os, s) : process_composed(din, is, dout, os, len, s);
+        if (r == FFTCONV_E_DEVICE) poisoned = true;
+        return r;
+    }
+
+    int process_device_steps(const float *din, size_t is, size_t in_step, float *dout, size_t os, size_t out_step,
+                             size_t len, size_t steps, hipStream_t s) {
+        for (size_t k = 0; k < steps; ++k)
+            if (int r = process_device(din + k * in_step, is, dout + k * out_step, os, len, s)) return r;
+        return FFTCONV_OK;
+    }
+
+    int process_host(const float *in, float *out, size_t len) {
+        if (int r = check_poisoned()) return r;
+        if (len > head_bs) return fail(FFTCONV_E_INVALID, "assertion failed: input.len() <= self.head_block_size");
+        if (len == 0) return FFTCONV_OK;
+        DeviceGuard g(device);
+        if (int r = order.enter(stream)) return r;
+        if (int r = scratch.ensure(I * len, O * len)) return r;
+        HIP_TRY(hipMemcpyAsync(scratch.in.p, in, I * len * sizeof(float), hipMemcpyHostToDevice, stream));
+        if (int r = process_device(scratch.in.p, len, scratch.out.p, len, len, stream)) return r;
+        HIP_TRY(hipMemcpyAsync(out, scratch.out.p, O * len * sizeof(float), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return FFTCONV_OK;
+    }
+
+    int reset() {  // :497-511
+        if (int r = check_poisoned()) return r;
+        DeviceGuard g(device);
+        if (int r = order.enter(stream)) return r;
+        for (auto *m : {head.get(), tail0.get(), tail.get()})
+            if (m)
+                if (int r = m->zero_state(stream)) return r;
+        for (auto *b : {&out0, &pre0, &out1, &pre1, &tin}) HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes(), stream));
+        tail_input_fill = 0;
+        precalculated_pos = 0;
+        HIP_TRY(hipStreamSynchronize(stream));
+        return FFTCONV_OK;
+    }
+
+    // #[derive(Clone)]: a deep device-side copy, including which buffer
+    // currently plays tail_output* / tail_precalculated*
+    int clone_from(const MatrixTwoStageCore &o) {
+        DeviceGuard g(o.device);
+        if (int r = o.order.drain(o.stream)) return r;
+        device = o.device; I = o.I; O = o.O; head_bs = o.head_bs; T = o.T;
+        fused = o.fused; poisoned = o.poisoned;
+        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        auto cl = [&](std::unique_ptr<MatrixCore> &dst, const std::unique_ptr<MatrixCore> &src) -> int {
+            if (!src) return FFTCONV_OK;
+            dst.reset(new (std::nothrow) MatrixCore());
+            if (!dst) return fail(FFTCONV_E_NOMEM, "out of host memory");
+            return dst->clone_from(*src, stream);
+        };
+        if (int r = cl(head, o.head)) return r;
+        if (int r = cl(tail0, o.tail0)) return r;
+        if (int r = cl(tail, o.tail)) return r;
+        if (int r = alloc_buffers()) return r;
+        auto map = [&](const float *p) -> float * {  // same role, this instance's buffer
+            if (p == o.out0.p) return out0.p;
+            if (p == o.pre0.p) return pre0.p;
+            if (p == o.out1.p) return out1.p;
+            return pre1.p;
+        };
+        tail_output0 = map(o.tail_output0); tail_precalculated0 = map(o.tail_precalculated0);
+        tail_output = map(o.tail_output); tail_precalculated = map(o.tail_precalculated);
+        const std::pair<DevPtr<float> *, const DevPtr<float> *> bufs[] = {
+            {&out0, &o.out0}, {&pre0, &o.pre0}, {&out1, &o.out1}, {&pre1, &o.pre1}, {&tin, &o.tin}};
+        for (auto &b : bufs)
+            HIP_TRY(hipMemcpyAsync(b.first->p, b.second->p, b.second->bytes(), hipMemcpyDeviceToDevice, stream));
+        tail_input_fill = o.tail_input_fill;
+        precalculated_pos = o.precalculated_pos;
+        HIP_TRY(hipStreamSynchronize(stream));
+        return FFTCONV_OK;
+    }
+};
+
 // W_N^k tables of the stand-alone Fft entry points, one per (device, N),
 // built on first use in f64 and kept for the process (the handles keep
 // their own); the same values as every handle's table for that N.  The first
@@ -2621,6 +2903,7 @@ struct fftconv_twostage { TwoStageCore core; };
 struct fftconv_crossfade { CrossfadeCore core; };
 struct fftconv_matrix { MatrixCore core; };
 struct fftconv_matrix_crossfade { MatrixCrossfadeCore core; };
+struct fftconv_matrix_twostage { MatrixTwoStageCore core; };
 
 extern "C" {
 
@@ -3126,5 +3409,68 @@ int fftconv_matrix_crossfade_set_fused(fftconv_matrix_crossfade *h, int on) {
     return FFTCONV_OK;
 }
 int fftconv_matrix_crossfade_path(const fftconv_matrix_crossfade *h) { return h ? h->core.path_next() : 0; }
+
+// ---- matrix two-stage ---------------------------------------------
+fftconv_matrix_twostage *fftconv_matrix_twostage_init(int device, size_t inputs, size_t outputs,
+                                                      const float *responses, size_t response_len,
+                                                      size_t response_stride, size_t max_block_size,
+                                                      size_t max_response_length) {
+    set_error("");
+    auto *h = new (std::nothrow) fftconv_matrix_twostage();
+    if (!h) { set_error("out of host memory"); return nullptr; }
+    int r = h->core.init(device, inputs, outputs, responses, response_len, response_stride, max_block_size,
+                         max_response_length);
+    return make_or_null(r, h);
+}
+int fftconv_matrix_twostage_update(fftconv_matrix_twostage *h, const float *, size_t, size_t) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return fail(FFTCONV_E_UNIMPLEMENTED, "not yet implemented (TwoStageFFTConvolver::update is todo!())");
+}
+int fftconv_matrix_twostage_reset(fftconv_matrix_twostage *h) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.reset();
+}
+int fftconv_matrix_twostage_process(fftconv_matrix_twostage *h, const float *input, float *output, size_t len) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.process_host(input, output, len);
+}
+int fftconv_matrix_twostage_process_device(fftconv_matrix_twostage *h, const float *d_input, size_t in_stride,
+                                           float *d_output, size_t out_stride, size_t len, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.device);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int r = h->core.order.enter(s)) return r;
+    return h->core.process_device(d_input, in_stride, d_output, out_stride, len, s);
+}
+int fftconv_matrix_twostage_process_device_steps(fftconv_matrix_twostage *h, const float *d_input, size_t in_stride,
+                                                 size_t in_step, float *d_output, size_t out_stride, size_t out_step,
+                                                 size_t len, size_t steps, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.device);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int r = h->core.order.enter(s)) return r;
+    return h->core.process_device_steps(d_input, in_stride, in_step, d_output, out_stride, out_step, len, steps, s);
+}
+fftconv_matrix_twostage *fftconv_matrix_twostage_clone(const fftconv_matrix_twostage *h) {
+    if (!h) { set_error("null handle"); return nullptr; }
+    auto *c = new (std::nothrow) fftconv_matrix_twostage();
+    if (!c) { set_error("out of host memory"); return nullptr; }
+    return make_or_null(c->core.clone_from(h->core), c);
+}
+void fftconv_matrix_twostage_destroy(fftconv_matrix_twostage *h) { delete h; }
+int fftconv_matrix_twostage_synchronize(fftconv_matrix_twostage *h) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.device);
+    return h->core.order.drain(h->core.stream);
+}
+size_t fftconv_matrix_twostage_inputs(const fftconv_matrix_twostage *h) { return h ? h->core.I : 0; }
+size_t fftconv_matrix_twostage_outputs(const fftconv_matrix_twostage *h) { return h ? h->core.O : 0; }
+size_t fftconv_matrix_twostage_tail_block_size(const fftconv_matrix_twostage *h) { return h ? h->core.T : 0; }
+int fftconv_matrix_twostage_set_fused(fftconv_matrix_twostage *h, int on) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    h->core.fused = on != 0;
+    return FFTCONV_OK;
+}
+int fftconv_matrix_twostage_path(const fftconv_matrix_twostage *h, size_t len) { return h ? h->core.path(len) : 0; }
 
 }  // extern "C"

@@ -418,4 +418,51 @@ struct MatrixXfArgs {
 // the chunk's two launches (32 <= B <= 8192)
 hipError_t launch_matrix_xf_chunk(int log2b, const MatrixXfArgs &a, hipStream_t s);
 
+// MatrixTwoStageConvolver (matrix_ts.hip): one aligned call -- a
+// whole head block on a block boundary of the tail period -- of the head [0]
+// and tail0 [1] matrices, which then have equal {current, active} and input
+// buffer fill 0, and delay lines that are equal row for row.
+struct MatrixTsArgs {
+    const float2 *H[2];    // [O][I][S][B] each
+    float2 *X[2];          // [I][S][B] each; the block's row is written to both
+    float *ovl[2];         // [O][B]
+    float2 *part[2];       // [O][P][B]
+    const float2 *tw;      // W_N^k, k < N = 2B
+    const float *in;       // the block of input 0 (+ in_stride per input)
+    long long in_stride;
+    float *out;            // the block of output 0 (+ out_stride per output)
+    long long out_stride;
+    float *tin;            // tail_input + tail_input_fill          (+ T per input)
+    float *tout0;          // tail_output0 + tail_input_fill        (+ T per output)
+    const float *p0;       // tail_precalculated0 + precalculated_pos (+ T per output)
+    const float *p1;       // tail_precalculated + precalculated_pos, or null (no tail stage)
+    long long T;
+    int I, O, S;
+    int P, rpp;            // as MatrixArgs
+    int cur, act;
+    int nt_h;              // nontemporal H streams (Variant::nt_matrix of one H)
+};
+// the call's two launches (32 <= B <= 8192)
+hipError_t launch_matrix_ts_block(int log2b, const MatrixTsArgs &a, hipStream_t s);
+
+// the two-stage matrix's sub-chunk on the composition path
+// (src/fft_convolver.rs:438-461): out[o] = (out[o] + p0[o]) + p1[o] for every
+// output, tail_input[i] <- in[i] for every input.
+struct MatrixTsAccumArgs {
+    float *out;
+    long long out_stride;
+    const float *p0;       // tail_precalculated0 [O][T], or null (no tail0 stage)
+    const float *p1;       // tail_precalculated  [O][T], or null (no tail stage)
+    long long T;
+    int pos;               // precalculated_pos
+    const float *in;
+    long long in_stride;
+    int sb;                // sub-chunk start within the call
+    float *tail_input;     // [I][T]
+    int fill;              // tail_input_fill before the append
+    int cnt;               // samples in the sub-chunk
+    int I, O;
+};
+hipError_t launch_matrix_ts_accum(const MatrixTsAccumArgs &a, hipStream_t s);
+
 }  // namespace fftconv

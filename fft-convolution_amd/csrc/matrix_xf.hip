@@ -47,13 +47,11 @@ __device__ __forceinline__ MatrixArgs xf_view(const MatrixXfArgs &a, int c) {
     return m;
 }
 
-// rows in flight of the two-H MAC (three streams per row instead of two: the
-// plain U still compiles without scratch), and the launches' dynamic LDS
+// the launches' dynamic LDS (launch A's MAC is matrix_mac_pair)
 template <int LOG2B, int NT>
 struct XGeo {
     using Gm = MGeo<LOG2B, NT>;
-    static constexpr int U = Gm::U;
-    static constexpr size_t lds_a = Gm::fft_bytes > 2 * Gm::red_bytes ? Gm::fft_bytes : 2 * Gm::red_bytes;
+    static constexpr size_t lds_a = Gm::lds_a_pair;
     static constexpr size_t lds_b = Gm::fft_bytes;
 };
 
@@ -94,118 +92,6 @@ __device__ __forceinline__ void xf_r2c(const MatrixXfArgs &a, int i, unsigned ch
     for (int m = tid; m < B; m += NT) row0[m] = row1[m] = real_post<LOG2B, NT>(Z, m, a.tw);
 }
 
-// matrix_mac for both convolvers in one pass over the rows: the walk, the
-// part bounds and each accumulator's order of additions are matrix_mac's; row
-// X[i][..] is loaded once (from X_A) and multiplied with H_A and H_B.
-template <int LOG2B, int NT, bool NTL>
-__device__ __forceinline__ void xf_mac_pair(const MatrixXfArgs &a, int o, int p, unsigned char *smem) {
-    using Gm = MGeo<LOG2B, NT>;
-    constexpr int F = Gm::F, G = Gm::G, SPT = Gm::SPT, U = XGeo<LOG2B, NT>::U;
-    const int tid = threadIdx.x;
-    const int f0 = G > 1 ? tid % F : tid;
-    const int g = G > 1 ? tid / F : 0;
-    const int act = a.act, am1 = act - 1;
-    const long long R = (long long)a.I * am1;
-    const long long r0 = (long long)p * a.rpp;
-    const long long r1 = r0 + a.rpp < R ? r0 + a.rpp : R;
-    DBG_CHECK(o >= 0 && o < a.O && p >= 0 && p < a.P, 53, o, p, a.O, a.P);  // (site 53: a part past `part`)
-    const int cm = a.cur % act;
-    const size_t hbase = (size_t)o * a.I * a.S * F;
-    const float4 *HA4 = reinterpret_cast<const float4 *>(a.H[0]) + hbase;
-    const float4 *HB4 = reinterpret_cast<const float4 *>(a.H[1]) + hbase;
-    const float4 *X4 = reinterpret_cast<const float4 *>(a.X[0]);
-
-    Acc2 accA[SPT], accB[SPT];
-#pragma unroll
-    for (int s = 0; s < SPT; ++s) {
-        accA[s].zero();
-        accB[s].zero();
-    }
-    long long r = r0 + g;
-    int i = 0, s = 1;
-    if (am1 > 0) {
-        i = (int)(r / am1);
-        s = 1 + (int)(r % am1);
-    }
-    auto advance = [&]() {
-        r += G;
-        s += G;
-        while (s > am1) {
-            s -= am1;
-            ++i;
-        }
-    };
-    auto hoff = [&]() {
-        DBG_CHECK(i >= 0 && i < a.I && s >= 1 && s < a.S, 52, i, s, a.I, a.S);  // (site 52: a MAC row past H / X)
-        return ((size_t)i * a.S + s) * F + f0;
-    };
-    auto xrow = [&]() {
-        int xi = cm + s;
-        if (xi >= act) xi -= act;
-        return X4 + ((size_t)i * a.S + xi) * F + f0;
-    };
-    while (r + (long long)(U - 1) * G < r1) {
-        float4 ha[U][SPT], hb[U][SPT], xv[U][SPT];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const size_t h = hoff();
-            const float4 *xp = xrow();
-#pragma unroll
-            for (int q = 0; q < SPT; ++q) {
-                ha[u][q] = ld4<NTL>(HA4 + h + q * NT);
-                hb[u][q] = ld4<NTL>(HB4 + h + q * NT);
-                xv[u][q] = ld4<false>(xp + q * NT);
-            }
-            advance();
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int q = 0; q < SPT; ++q) {
-                accA[q].mac(ha[u][q], xv[u][q]);
-                accB[q].mac(hb[u][q], xv[u][q]);
-            }
-    }
-    while (r < r1) {
-        const size_t h = hoff();
-        const float4 *xp = xrow();
-#pragma unroll
-        for (int q = 0; q < SPT; ++q) {
-            const float4 x = ld4<false>(xp + q * NT);
-            accA[q].mac(ld4<NTL>(HA4 + h + q * NT), x);
-            accB[q].mac(ld4<NTL>(HB4 + h + q * NT), x);
-        }
-        advance();
-    }
-
-    const size_t pbase = ((size_t)o * a.P + p) * F;
-    float4 *dstA = reinterpret_cast<float4 *>(a.part[0]) + pbase;
-    float4 *dstB = reinterpret_cast<float4 *>(a.part[1]) + pbase;
-    if constexpr (G > 1) {
-        float4 *redA = reinterpret_cast<float4 *>(smem);
-        float4 *redB = redA + NT;
-        redA[g * F + f0] = accA[0].get(f0);
-        redB[g * F + f0] = accB[0].get(f0);
-        __syncthreads();
-        if (tid < F) {
-            float4 v = redA[f0], w = redB[f0];
-#pragma unroll
-            for (int q = 1; q < G; ++q) {
-                v = vadd(v, redA[q * F + f0]);
-                w = vadd(w, redB[q * F + f0]);
-            }
-            dstA[f0] = v;
-            dstB[f0] = w;
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < SPT; ++q) {
-            dstA[f0 + q * NT] = accA[q].get(f0 + q * NT);
-            dstB[f0 + q * NT] = accB[q].get(f0 + q * NT);
-        }
-    }
-}
-
 template <int LOG2B, int NT, bool NTL>
 __global__ __launch_bounds__(NT) void matrix_xf_a_kernel(MatrixXfArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -220,7 +106,7 @@ __global__ __launch_bounds__(NT) void matrix_xf_a_kernel(MatrixXfArgs a) {
     }
     const int m = b - a.I;
     if (a.live == 3)
-        xf_mac_pair<LOG2B, NT, NTL>(a, m / a.P, m % a.P, smem);
+        matrix_mac_pair<LOG2B, NT, NTL>(a, m / a.P, m % a.P, smem);
     else
         matrix_mac<LOG2B, NT, NTL>(xf_view(a, a.live == 1 ? 0 : 1), m / a.P, m % a.P, smem);
 }

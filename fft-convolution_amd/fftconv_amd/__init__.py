@@ -134,6 +134,20 @@ SIGNATURES = {
     "fftconv_matrix_crossfade_outputs": (_sz, [_vp]),
     "fftconv_matrix_crossfade_set_fused": (_i, [_vp, _i]),
     "fftconv_matrix_crossfade_path": (_i, [_vp]),
+    "fftconv_matrix_twostage_init": (_vp, [_i, _sz, _sz, _fp, _sz, _sz, _sz, _sz]),
+    "fftconv_matrix_twostage_update": (_i, [_vp, _fp, _sz, _sz]),
+    "fftconv_matrix_twostage_reset": (_i, [_vp]),
+    "fftconv_matrix_twostage_process": (_i, [_vp, _fp, _fp, _sz]),
+    "fftconv_matrix_twostage_process_device": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_twostage_process_device_steps": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _sz, _sz, _vp]),
+    "fftconv_matrix_twostage_clone": (_vp, [_vp]),
+    "fftconv_matrix_twostage_destroy": (None, [_vp]),
+    "fftconv_matrix_twostage_synchronize": (_i, [_vp]),
+    "fftconv_matrix_twostage_inputs": (_sz, [_vp]),
+    "fftconv_matrix_twostage_outputs": (_sz, [_vp]),
+    "fftconv_matrix_twostage_tail_block_size": (_sz, [_vp]),
+    "fftconv_matrix_twostage_set_fused": (_i, [_vp, _i]),
+    "fftconv_matrix_twostage_path": (_i, [_vp, _sz]),
 }
 
 
@@ -676,9 +690,66 @@ class MatrixCrossfadeConvolver(_Base):
         return int(lib().fftconv_matrix_crossfade_path(self._h))
 
 
+class MatrixTwoStageConvolver(_Base):
+    """Two-stage partitioning for the matrix (fftconv.h,
+    "MatrixTwoStageConvolver"): inputs x outputs TwoStageFFTConvolver instances
+    in lockstep -- a head and a first tail stage of block max_block_size, a tail
+    of block tail_block_size -- with one delay line per input and stage."""
+
+    _prefix = "matrix_twostage"
+
+    def __init__(self, h, inputs: int, outputs: int):
+        super().__init__(h, inputs)
+        self.inputs = inputs
+        self.outputs = outputs
+
+    @classmethod
+    def init(cls, responses, max_block_size: int, max_response_length: int, device: int = 0):
+        """responses[O][I][len]: h[o][i] is the response from input i to output o."""
+        r = MatrixConvolver._pairs(responses)
+        O, I, n = r.shape
+        h = lib().fftconv_matrix_twostage_init(device, I, O, _p(r), n, n, max_block_size, max_response_length)
+        return cls(_handle(h), I, O)
+
+    def update(self, responses):
+        """todo!() in the reference (src/fft_convolver.rs:408-410): raises
+        NotImplementedInReference, the handle is unchanged."""
+        r = MatrixConvolver._pairs(responses, self.inputs, self.outputs)
+        _check(lib().fftconv_matrix_twostage_update(self._h, _p(r), r.shape[2], r.shape[2]))
+
+    def reset(self):
+        _check(lib().fftconv_matrix_twostage_reset(self._h))
+
+    def process(self, inp) -> np.ndarray:
+        """x[inputs][n <= max_block_size] -> y[outputs][n]."""
+        x = _f32(inp)
+        if x.ndim != 2 or x.shape[0] != self.inputs:
+            raise ValueError(f"input must be [{self.inputs}][n]")
+        n = x.shape[1]
+        y = np.zeros((self.outputs, n), np.float32)
+        _check(lib().fftconv_matrix_twostage_process(self._h, _p(x), _p(y), n))
+        return y
+
+    def clone(self):
+        return MatrixTwoStageConvolver(_handle(lib().fftconv_matrix_twostage_clone(self._h)), self.inputs,
+                                       self.outputs)
+
+    @property
+    def tail_block_size(self) -> int:
+        return int(lib().fftconv_matrix_twostage_tail_block_size(self._h))
+
+    def set_fused(self, on: bool):
+        """False: every call takes the composition path (tests, A/B runs)."""
+        _check(lib().fftconv_matrix_twostage_set_fused(self._h, 1 if on else 0))
+
+    def path(self, n: int) -> int:
+        """The path the next process() of n samples takes: 0 composition, 1 fused."""
+        return int(lib().fftconv_matrix_twostage_path(self._h, n))
+
+
 __all__ = [
     "Fft", "FFTConvolver", "TwoStageFFTConvolver", "CrossfadeConvolver", "MatrixConvolver",
-    "MatrixCrossfadeConvolver", "ConvolutionPanic",
+    "MatrixCrossfadeConvolver", "MatrixTwoStageConvolver", "ConvolutionPanic",
     "NotImplementedInReference", "DeviceError", "complex_size", "compute_tail_block_size", "device_count",
     "lib", "LIB_PATH", "SIGNATURES",
 ]

@@ -62,6 +62,7 @@ typedef struct fftconv_twostage fftconv_twostage;   /* TwoStageFFTConvolver src/
 typedef struct fftconv_crossfade fftconv_crossfade; /* CrossfadeConvolver<FFTConvolver | TwoStageFFTConvolver> src/crossfade_convolver.rs:10-105 */
 typedef struct fftconv_matrix fftconv_matrix;       /* inputs x outputs FFTConvolver instances, summed per output (below) */
 typedef struct fftconv_matrix_crossfade fftconv_matrix_crossfade; /* inputs x outputs CrossfadeConvolver<FFTConvolver> instances (below) */
+typedef struct fftconv_matrix_twostage fftconv_matrix_twostage;   /* inputs x outputs TwoStageFFTConvolver instances (below) */
 
 /* ---- library ----------------------------------------------------------- */
 int fftconv_abi_version(void);
@@ -450,6 +451,85 @@ int fftconv_matrix_crossfade_set_fused(fftconv_matrix_crossfade *h, int on);
 /* the path (0, 1 or 2 above) the next process() would take, a pending
  * response included */
 int fftconv_matrix_crossfade_path(const fftconv_matrix_crossfade *h);
+
+/* ---- MatrixTwoStageConvolver: two-stage partitioning for the matrix ----
+ * A matrix two-stage convolver (inputs I, outputs O, head block max_block_size,
+ * max_response_length L) behaves as I*O reference TwoStageFFTConvolver
+ * instances (o, i) (src/fft_convolver.rs:323-526), all created and reset
+ * together with the same lengths: instance (o, i) processes input i with the
+ * same calls, output o is the sum over i.  Everything in process (:412-495)
+ * that is not a convolver -- tail_input_fill, precalculated_pos, the two buffer
+ * swaps, the sub-chunk loop -- runs in lockstep, so the handle keeps one copy
+ * of those scalars on the host.  The device keeps tail_output0,
+ * tail_precalculated0, tail_output and tail_precalculated summed per output
+ * ([O][T] each) and tail_input per input ([I][T]): results equal the summed
+ * instances within f32 rounding, not bitwise.
+ * Stages (:340-406), T = fftconv_compute_tail_block_size(max_block_size, L),
+ * each pair's response zero-extended to L first; each stage is a matrix as
+ * fftconv_matrix_*:
+ *   head   padded_ir[0 .. min(L, T)],               block max_block_size
+ *   tail0  padded_ir[T .. T + min(L - T, T)],       block max_block_size, only when L > T
+ *   tail   padded_ir[2T .. L],                      block T,              only when L > 2T
+ * An absent stage contributes nothing and is skipped (the reference's Default
+ * convolver outputs zeros).
+ * The plain matrix's departures carry over: non-finite samples are outside the
+ * parity contract; outputs do not depend on `outputs`, so a matrix split by
+ * outputs over several handles computes bit-identical rows.
+ * Mirrored from the reference:
+ *  - process: len > max_block_size is FFTCONV_E_INVALID (the assert at :414).
+ *    A head block size that does not divide T runs tail_input past its end
+ *    (:459-460): FFTCONV_E_INVALID at the call where the reference panics.
+ *  - update is todo!() (:408-410): FFTCONV_E_UNIMPLEMENTED, handle unchanged.
+ *  - reset: :497-511.  clone: a deep copy, mid-period state included.
+ * Limits: 32 <= next_power_of_two(max_block_size) <= 8192 as for the plain
+ * matrix, and T <= 8192 (the tail is a matrix of block T), else
+ * FFTCONV_E_UNSUPPORTED before anything is allocated (head 512 / L 262,144
+ * gives T 16,384; head 64 and head 256 / L 262,144 are supported).  inputs == 0,
+ * outputs == 0 or response_len > L is FFTCONV_E_INVALID; init returns NULL on
+ * error (fftconv_last_error).  Pairs and strides as fftconv_matrix_*.
+ * Everything runs on one stream, in stream order; the tail's block-T
+ * convolution at the end of a period is enqueued inline, where the reference
+ * runs it (:479-486), so the call that ends a period carries it.
+ * Paths (fftconv_matrix_twostage_path) -- both compute the same bits:
+ *   0  composition: head, then per sub-chunk one small kernel (the sums of
+ *      :438-454 and the copy into tail_input), tail0 on each completed head
+ *      block, the swaps and the tail at the end of the period.
+ *   1  fused: head, the sub-chunk and tail0 in the plain matrix's two launches
+ *      -- one forward transform per input for both delay lines, every delay-
+ *      line row streamed once for both responses.  Taken when the call is
+ *      aligned (len == max_block_size, a power of two; tail_input_fill a
+ *      multiple of it; the head's input buffer empty), tail0 exists and head
+ *      and tail0 have equal segment counts. */
+fftconv_matrix_twostage *fftconv_matrix_twostage_init(int device, size_t inputs, size_t outputs,
+                                                      const float *responses, size_t response_len,
+                                                      size_t response_stride, size_t max_block_size,
+                                                      size_t max_response_length);
+/* :408-410: FFTCONV_E_UNIMPLEMENTED */
+int fftconv_matrix_twostage_update(fftconv_matrix_twostage *h, const float *responses, size_t response_len,
+                                   size_t response_stride);
+int fftconv_matrix_twostage_reset(fftconv_matrix_twostage *h); /* :497-511 */
+/* input [inputs][len], output [outputs][len], host memory. */
+int fftconv_matrix_twostage_process(fftconv_matrix_twostage *h, const float *input, float *output, size_t len);
+/* device memory, stream-ordered: input i at d_input + i * in_stride, output o
+ * at d_output + o * out_stride (strides in floats). */
+int fftconv_matrix_twostage_process_device(fftconv_matrix_twostage *h, const float *d_input, size_t in_stride,
+                                           float *d_output, size_t out_stride, size_t len, void *hip_stream);
+/* `steps` consecutive process_device calls; the same bits as the separate calls. */
+int fftconv_matrix_twostage_process_device_steps(fftconv_matrix_twostage *h, const float *d_input,
+                                                 size_t in_stride, size_t in_step, float *d_output,
+                                                 size_t out_stride, size_t out_step, size_t len, size_t steps,
+                                                 void *hip_stream);
+fftconv_matrix_twostage *fftconv_matrix_twostage_clone(const fftconv_matrix_twostage *h);
+void fftconv_matrix_twostage_destroy(fftconv_matrix_twostage *h);
+int fftconv_matrix_twostage_synchronize(fftconv_matrix_twostage *h);
+size_t fftconv_matrix_twostage_inputs(const fftconv_matrix_twostage *h);
+size_t fftconv_matrix_twostage_outputs(const fftconv_matrix_twostage *h);
+size_t fftconv_matrix_twostage_tail_block_size(const fftconv_matrix_twostage *h);
+/* tests and A/B runs: on = 0 makes every call of this handle take the
+ * composition path (default 1); a clone inherits the setting. */
+int fftconv_matrix_twostage_set_fused(fftconv_matrix_twostage *h, int on);
+/* the path (0 or 1 above) the next process() of `len` samples would take */
+int fftconv_matrix_twostage_path(const fftconv_matrix_twostage *h, size_t len);
 
 #ifdef __cplusplus
 }
