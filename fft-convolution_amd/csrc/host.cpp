@@ -314,6 +314,9 @@ struct UniformCore {
     DevPtr<int4> lav;
     mutable bool view_ok = false;
     bool la_all = true;           // next lookahead launch re-anchors every channel
+    // the per-call batch of steps (la_batch.hpp): per channel the first step
+    // its fix-up launch runs
+    DevPtr<int> la_res;
     // long-block path (B > 2^kMaxLog2Fused, large.hip): per-call progress,
     // the inverse's scratch, the geometry's tables; lg_whole: every call
     // since init / reset was whole blocks, so every channel's buffer is empty
@@ -398,6 +401,7 @@ struct UniformCore {
             if (const char *e = getenv("FFTCONV_LA_POISON"); e && atoi(e) > 0)
                 HIP_TRY(hipMemsetAsync(laW.p, 0xff, laW.bytes(), stream));
             if (int r = lav.alloc(2 * C)) return r;
+            if (int r = la_res.alloc(C)) return r;
             view_ok = false;
             if (const char *e = getenv("FFTCONV_LA_PROBE"); e && atoi(e) > 0) {
                 if (int r = la_probe.alloc(1)) return r;
@@ -715,6 +719,41 @@ struct UniformCore {
         return FFTCONV_OK;
     }
 
+    // `steps` one-block calls of a lookahead batch whose blocks are all at
+    // hand: chunks of up to LA_BATCH_MAX steps, four launches each
+    // (la_batch.hpp), the same bits as one launch per block.  Not for a
+    // handle that is tracing or probing its per-block launches, nor under
+    // VARIANT_NORUN (one launch per call) or VARIANT_LAFULL (the per-step
+    // full pass, which tests compare against).  A chunk takes the window
+    // buffer, so the per-block launch after it is an entry launch (la_all):
+    // short calls stay per-block while the windows are live, and every call
+    // takes the batch once they are dropped anyway.
+    bool la_batch_ready(size_t n, size_t steps) const {
+        const Variant v = Variant::current();
+        return n == B && la_ready(n) && la_res.p && lav.p && !trace_slots && !la_probe.p &&
+               !v.has(VARIANT_NORUN | VARIANT_LAFULL) && steps >= 1 && (steps >= (size_t)LA_BATCH_MIN || la_all);
+    }
+    int la_batch(const float *din, size_t is, size_t in_step, float *dout, size_t os, size_t out_step, size_t steps,
+                 hipStream_t s) {
+        for (size_t k0 = 0; k0 < steps; k0 += LA_BATCH_MAX) {
+            const int k = (int)std::min<size_t>(LA_BATCH_MAX, steps - k0);
+            ProcArgs a{};
+            a.job[0] = job_raw(din + k0 * in_step, is, dout + k0 * out_step, os, B);
+            a.tw = tw.p;
+            a.njobs = 1;
+            a.laW = laW.p;
+            const LaBatchArgs b{(long long)in_step, (long long)out_step, k, la_seq, la_res.p};
+            HIP_TRY(launch_la_batch(log2b, a, b, (int)C, s));
+            // as k per-block launches leave the clocks; no window is live and
+            // the anchors' copies of the state words are stale
+            la_t += (unsigned long long)k;
+            if (k & 1) la_seq = 3 - la_seq;
+            la_all = true;
+            view_ok = false;
+        }
+        return FFTCONV_OK;
+    }
+
     // `steps` consecutive process() calls (fftconv_uniform_process_device_steps).
     // A batch on the generic / pipelined step (no lookahead, no far-row
     // windows, B <= 512) whose workgroups fit the chip twice over runs them
@@ -722,6 +761,8 @@ struct UniformCore {
     // process_job per call -- the same bits as one launch per call).
     int process_device_steps(const float *din, size_t is, size_t in_step, float *dout, size_t os, size_t out_step,
                              size_t n, size_t steps, hipStream_t s) {
+        if (C && in_step <= (size_t)LLONG_MAX && out_step <= (size_t)LLONG_MAX && la_batch_ready(n, steps))
+            return la_batch(din, is, in_step, dout, os, out_step, steps, s);
         int ncu = 0;
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) ncu = 0;
         if (steps >= 2 && n > 0 && n <= (size_t)INT32_MAX && !la_W && !large && !gw_p && !trace_slots &&
@@ -779,6 +820,8 @@ struct UniformCore {
         la_ok = o.la_ok; la_W = o.la_W; la_t = o.la_t; la_seq = o.la_seq; la_all = o.la_all;
         if (o.lav.n)
             if (int r = lav.alloc(o.lav.n)) return r;
+        if (o.la_res.n)
+            if (int r = la_res.alloc(o.la_res.n)) return r;
         view_ok = false;  // (copied from `state` before the clone's first lookahead launch)
         if (int r = cp(gwin, o.gwin)) return r;
         gw_ok = o.gw_ok; gw_p = o.gw_p; gw_t = o.gw_t;

@@ -300,6 +300,26 @@ hipError_t launch_process_la(int log2b, const ProcArgs &a, int channels, hipStre
 // current H and FDL (anchors only), then their state words pointed at them
 hipError_t launch_la_rebuild(int log2b, const ProcArgs &a, int channels, hipStream_t s);
 
+// A chunk of k consecutive one-block lookahead steps whose blocks are all at
+// hand (process_device_steps), in four launches (la_batch.hpp: spectra, walk,
+// finish, fix-up) instead of k.  Step j is a.job[0] with in / out advanced by
+// j * in_step / out_step floats.  The chunk's staging and pre rows take the
+// window buffer a.laW, so it leaves no live window.
+constexpr int LA_BATCH_MAX = 64;  // steps per chunk (2 x 64 rows of the channel's 2 x 84 window rows)
+// the shortest call that takes the batch while the windows are live: below
+// it the per-block launches' 36.5 row transfers per step cost less than the
+// batch's one pass over H and the FDL spread over the call (cfg2, same
+// process: 12-step calls 18.5 against 16.6 us per step per block, 16-step
+// calls 14.5 against 16.6)
+constexpr int LA_BATCH_MIN = 16;
+struct LaBatchArgs {
+    long long in_step, out_step;
+    int k;                 // steps of the chunk, 1..LA_BATCH_MAX
+    int seq0;              // the launch tag step 0 would carry (ProcArgs::la_seq), alternating per step
+    int *resume;           // [C]: the first step the fix-up launch runs for the channel (k = none)
+};
+hipError_t launch_la_batch(int log2b, const ProcArgs &a, const LaBatchArgs &b, int channels, hipStream_t s);
+
 // Two-stage tail0 deferred to the end of its period (src/fft_convolver.rs
 // :464-475: tail_output0 is first read after the period's swap).  pa.job[0]
 // is tail0's job with in = tail_input + off, out = tail_output0 + off (both

@@ -180,28 +180,38 @@ __device__ __forceinline__ const float2 *la_xsrc(const ProcArgs &a, int jb, size
 // rows in the chain's order.  X rows live in a register ring indexed by the
 // walk position e; each row of H and of the FDL is loaded once, LA_U ahead.
 // (Callers pass hi > lo.)
+// The X rows come from a source XS: ld(voff, age) = the row `age` steps older
+// than the anchor's ring position.  LaRingX is the FDL ring itself; the
+// per-call batch (la_batch.hpp) reads the call's own blocks (age < 0) from
+// its staged spectra.
 // ---------------------------------------------------------------------------
-template <int LOG2B, bool ASC, bool NTL, int JW, int U = LA_U>
-__device__ __forceinline__ void la_walk(LaAcc (&acc)[JW], const RowStream &hs, const RowStream &xs, int voff,
-                                        bool z0, int lo, int hi, int j0, int cur, int act) {
+template <int LOG2B>
+struct LaRingX {
+    const RowStream &xs;
+    int cur, act;
+    template <bool NTL>
+    __device__ __forceinline__ float4 ld(int voff, int age) const {
+        int r = cur + age;
+        if (r >= act) r -= act;
+        return xs.ld4<NTL>(voff, r * ((1 << LOG2B) * (int)sizeof(float2)));
+    }
+};
+template <int LOG2B, bool ASC, bool NTL, int JW, int U, class XS>
+__device__ __forceinline__ void la_walk_x(LaAcc (&acc)[JW], const RowStream &hs, const XS &xs, int voff, bool z0,
+                                          int lo, int hi, int j0) {
     constexpr int ROWB = (1 << LOG2B) * (int)sizeof(float2);
     constexpr int RS = JW + U;                         // X ring: window + prefetch
     constexpr int UNR = RS % U == 0 ? RS : RS * U;  // static ring slots
     const int n = hi - lo;
     const int ne = n + JW - 1;
-    auto xoff = [&](int e) {
-        const int age = ASC ? lo - j0 - JW + e : hi - 2 - j0 - e;
-        int r = cur + age;
-        if (r >= act) r -= act;
-        return r * ROWB;
-    };
+    auto xage = [&](int e) { return ASC ? lo - j0 - JW + e : hi - 2 - j0 - e; };
     auto hoff = [&](int k) { return (ASC ? lo + k : hi - 1 - k) * ROWB; };
     // rows past the walk are loaded from an out-of-range buffer offset (zero,
     // no memory access): no branches around the loads, no register copies
     auto vo = [&](bool in) { return in ? voff : LA_OOB; };
     float4 xr[RS], hr[U];
 #pragma unroll
-    for (int e = 0; e < RS - 1; ++e) xr[e] = xs.ld4<NTL>(vo(e < ne), xoff(e < ne ? e : 0));
+    for (int e = 0; e < RS - 1; ++e) xr[e] = xs.template ld<NTL>(vo(e < ne), xage(e < ne ? e : 0));
 #pragma unroll
     for (int k = 0; k < U; ++k) hr[k] = hs.ld4<NTL>(vo(k < n), hoff(k < n ? k : 0));
 #pragma nounroll
@@ -215,12 +225,17 @@ __device__ __forceinline__ void la_walk(LaAcc (&acc)[JW], const RowStream &hs, c
             for (int jj = 0; jj < JW; ++jj) acc[jj].mac(h, xr[(ASC ? u + JW - 1 - jj : u + jj) % RS]);
             const bool hin = k + U < n, xin = k + RS - 1 < ne;
             hr[u % U] = hs.ld4<NTL>(vo(hin), hoff(hin ? k + U : 0));
-            xr[(u + RS - 1) % RS] = xs.ld4<NTL>(vo(xin), xoff(xin ? k + RS - 1 : 0));
+            xr[(u + RS - 1) % RS] = xs.template ld<NTL>(vo(xin), xage(xin ? k + RS - 1 : 0));
             // keep the issue order: the scheduler would otherwise hoist the
             // loads of later rows and run out of registers
             __builtin_amdgcn_sched_barrier(0);
         }
     }
+}
+template <int LOG2B, bool ASC, bool NTL, int JW, int U = LA_U>
+__device__ __forceinline__ void la_walk(LaAcc (&acc)[JW], const RowStream &hs, const RowStream &xs, int voff,
+                                        bool z0, int lo, int hi, int j0, int cur, int act) {
+    la_walk_x<LOG2B, ASC, NTL, JW, U>(acc, hs, LaRingX<LOG2B>{xs, cur, act}, voff, z0, lo, hi, j0);
 }
 
 // One chain for the current step (X age i), the same rows in the same order

@@ -1,5 +1,6 @@
 // lookahead.hip -- the lookahead step (la.hpp: upols_la_kernel), the window
-// rebuild after update / reset / init, and their launchers.
+// rebuild after update / reset / init, the per-call batch of steps
+// (la_batch.hpp), and their launchers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -7,6 +8,7 @@
 
 #include "kernels.hpp"
 #include "la.hpp"
+#include "la_batch.hpp"
 #include "launch.hpp"
 
 namespace fftconv {
@@ -200,6 +202,61 @@ static hipError_t launch_rebuild_t(const ProcArgs &a, int channels, hipStream_t 
 hipError_t launch_la_rebuild(int log2b, const ProcArgs &a, int channels, hipStream_t s) {
     if (channels <= 0) return hipSuccess;
     return dispatch_fused(log2b, [&](auto L) { return launch_rebuild_t<L()>(a, channels, s); });
+}
+
+// ---------------------------------------------------------------------------
+// A chunk of one-block steps in four launches (la_batch.hpp), all on stream s:
+// each reads what the one before it wrote.
+// ---------------------------------------------------------------------------
+template <int LOG2B>
+static hipError_t launch_batch_t(const ProcArgs &a, const LaBatchArgs &b, int channels, hipStream_t s) {
+    if constexpr (LOG2B < 7 || LOG2B > 9) {
+        return hipErrorNotSupported;
+    } else {
+        using LG = LaGeo<LOG2B>;
+        if (!a.laW || !b.resume || a.njobs != 1 || a.job[0].n != (1 << LOG2B) || b.k < 1 || b.k > LA_BATCH_MAX ||
+            (b.seq0 != 1 && b.seq0 != 2) || a.la_mix || a.job[0].add0 || a.job[0].tin || a.la_trace ||
+            a.la_probe_cnt)
+            return hipErrorInvalidValue;
+        ProcArgs args = a;
+        args.pipe = 0;
+        args.lag = 0;
+        args.la_channels = channels;
+        args.la_c0 = 0;
+        args.la_rebuild = 0;
+        args.la_all = -1;
+        args.la_n[0] = args.la_n[1] = args.la_n[2] = 0;
+        args.la_l1in2 = 0;
+        args.la_nlv = la_nlv(a.job[0].S);
+        args.job[0].mcall = 1;
+        args.job[0].mk = 0;
+        args.job[0].sview = nullptr;
+        args.job[0].vnext = nullptr;
+        if (hipError_t e = launch_dyn(la_batch_spectra_kernel<LOG2B>, dim3(channels, (b.k + 3) / 4), dim3(LA_NT),
+                                      LabSpectra<LOG2B>::bytes, s, args, b);
+            e != hipSuccess)
+            return e;
+        const int wga = LG::NSL * ((b.k + LA_JW - 1) / LA_JW);
+        if (hipError_t e = launch_dyn(la_batch_walk_kernel<LOG2B, FFTCONV_LAB_U>, dim3((channels + 7) / 8 * 8 * wga),
+                                      dim3(LA_NT), LabWalk<LOG2B>::bytes, s, args, b);
+            e != hipSuccess)
+            return e;
+        if (hipError_t e = launch_dyn(la_batch_finish_kernel<LOG2B>, dim3(channels), dim3(LA_NT),
+                                      LabFinish<LOG2B>::bytes, s, args, b);
+            e != hipSuccess)
+            return e;
+        // the fix-up's steps are la_fallback's: the lookahead step of one
+        // channel or the generic step
+        constexpr size_t lds = LabFixup<LOG2B>::bytes;
+        const bool ntl = Variant::current().nt_stream(Variant::stream_bytes(channels, a.job[0].S, LOG2B));
+        auto fix = ntl ? la_batch_fixup_kernel<LOG2B, true> : la_batch_fixup_kernel<LOG2B, false>;
+        return launch_dyn(fix, dim3(channels), dim3(LA_NT), lds, s, args, b);
+    }
+}
+
+hipError_t launch_la_batch(int log2b, const ProcArgs &a, const LaBatchArgs &b, int channels, hipStream_t s) {
+    if (channels <= 0) return hipSuccess;
+    return dispatch_fused(log2b, [&](auto L) { return launch_batch_t<L()>(a, b, channels, s); });
 }
 
 }  // namespace fftconv

@@ -25,7 +25,8 @@ namespace fftconv {
 //   9    512    T0FUSED    launch  deferred tail0 at B = 64: the five-kernel flush (else the ONE fused kernel;
 //                                  bit-identical -- despite its name the bit turns the fusion off)
 //   10   1024   NOGW       launch  B >= 1024: no far-row windows, every step sums its far rows itself (tests)
-//   11   2048   NORUN      launch  process_device_steps: one launch per call (else a run of calls per launch)
+//   11   2048   NORUN      launch  process_device_steps: one launch per call (else a run of calls per launch,
+//                                  or on the lookahead step a batch of steps in four launches, la_batch.hpp)
 //   12   4096   NORUNLDS   launch  runs stream the FDL / IR rows from memory (else from LDS copies; same bits).
 //                                  NOT selectable: the ABI accepts 0..4095 and set_variant masks with 4095,
 //                                  so the branch that reads it never runs

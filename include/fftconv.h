@@ -206,7 +206,21 @@ int fftconv_uniform_process_device(fftconv_uniform *h, const float *d_input, siz
 /* `steps` consecutive process() calls of `len` samples each, from one host
  * call: call k reads d_input + k*in_step (channel stride in_stride) and writes
  * d_output + k*out_step.  Identical to `steps` calls of _process_device; it
- * removes the per-call host overhead when blocks are already resident. */
+ * removes the per-call host overhead when blocks are already resident.
+ *
+ * A standalone batch on the lookahead step (128 <= B <= 512, 40 or more
+ * segments) called with len == block size runs a call of 16 or more steps as
+ * a batch: four launches per chunk of up to 64 steps instead of one per step,
+ * each IR row and delay-line row read once per chunk (bit-identical; cfg2:
+ * 11.4 us per step in 32-step calls against 16.6).  The batch takes the
+ * handle's partial-sum windows, so the next _process_device call (or a steps
+ * call shorter than 16) re-enters with a full sum of every channel, ~400 us
+ * at cfg2, and until it has, steps calls of any length take the batch.  A
+ * caller that alternates steps calls and single _process_device calls pays
+ * that entry at every switch (612 us per pair of one call and one 16-step
+ * call, measured): it should submit everything through one of the two, or
+ * set kernel-variant bit 11 (2048), which keeps _process_device_steps on one
+ * launch per step. */
 int fftconv_uniform_process_device_steps(fftconv_uniform *h, const float *d_input, size_t in_stride,
                                          size_t in_step, float *d_output, size_t out_stride,
                                          size_t out_step, size_t len, size_t steps, void *hip_stream);
