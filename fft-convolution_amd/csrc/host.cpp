@@ -2087,6 +2087,287 @@ struct MatrixCore {
 };
 
 // ---------------------------------------------------------------------------
+// SparseMatrixCore -- N FFTConvolver instances in lockstep, one per listed
+// (output, input) pair: the MatrixCore's scheme over a CSR
+// pattern that is fixed for the life of the handle.  H, the staging and the
+// IR transforms cover the N pairs only; launch A's MAC grid is the compact
+// sum of the outputs' P_o, found through a device plan that is rebuilt on the
+// stream whenever active_seg_count changes (init, update).
+// ---------------------------------------------------------------------------
+struct SparseMatrixCore {
+    int device = 0;
+    size_t I = 0, O = 0, N = 0;
+    size_t ir_len = 0;    // max_response_length
+    size_t B = 0;
+    int log2b = 0;
+    size_t S = 0;         // seg_count
+    size_t PTmax = 0;     // sum of P_o at active = S (the rows of `part`)
+    size_t PT = 0;        // sum of P_o at the current active
+    size_t cur = 0, act = 0, fill = 0;
+    std::vector<int> rowptr, col;  // the host's copy of the pattern
+    DevPtr<float2> H, X, pre, part, tw;
+    DevPtr<float> ovl, ib, staging;
+    DevPtr<int> d_rowptr, d_col, plan;
+    DevPtr<int4> wg;      // [PTmax] the MAC workgroups' descriptors, rebuilt with the plan
+    hipStream_t stream = nullptr;
+    Scratch scratch;
+    PinnedStage hstage;
+    mutable StreamOrder order;
+
+    ~SparseMatrixCore() {
+        if (stream) {
+            DeviceGuard g(device);
+            (void)order.drain(stream);
+            (void)hipStreamDestroy(stream);
+        }
+    }
+
+    size_t pairs_of(size_t o) const { return (size_t)(rowptr[o + 1] - rowptr[o]); }
+    int output_parts(size_t o) const { return matrix_mac_parts((int)pairs_of(o), log2b, (int)S, (int)act); }
+    size_t total_parts(size_t active) const {
+        size_t t = 0;
+        for (size_t o = 0; o < O; ++o) t += (size_t)matrix_mac_parts((int)pairs_of(o), log2b, (int)S, (int)active);
+        return t;
+    }
+    // the device plan for the current `act`, behind the stream's earlier work
+    // (launches that read the previous plan) and ahead of its later launches
+    int rebuild_plan(hipStream_t s) {
+        PT = total_parts(act);
+        HIP_TRY(launch_matrix_sp_plan(d_rowptr.p, plan.p, wg.p, (int)O, (int)act, s));
+        return FFTCONV_OK;
+    }
+
+    static int check_pattern(size_t inputs, size_t outputs, size_t pairs, const uint32_t *po, const uint32_t *pi) {
+        if (inputs == 0 || outputs == 0)
+            return fail(FFTCONV_E_INVALID, "a matrix needs at least one input and one output");
+        if (pairs == 0 || !po || !pi) return fail(FFTCONV_E_INVALID, "a sparse matrix needs at least one pair");
+        if (inputs > (size_t)INT32_MAX || outputs > (size_t)INT32_MAX || pairs > (size_t)INT32_MAX)
+            return fail(FFTCONV_E_UNSUPPORTED, "geometry exceeds 32-bit indexing");
+        for (size_t n = 0; n < pairs; ++n) {
+            if (po[n] >= outputs || pi[n] >= inputs)
+                return fail(FFTCONV_E_INVALID, "pair " + std::to_string(n) + " is out of range");
+            if (n > 0 && (po[n] < po[n - 1] || (po[n] == po[n - 1] && pi[n] <= pi[n - 1])))
+                return fail(FFTCONV_E_INVALID, "the pair list is not strictly ascending in (output, input) at pair " +
+                                                   std::to_string(n));
+        }
+        return FFTCONV_OK;
+    }
+
+    int alloc_geometry(int dev, size_t inputs, size_t outputs, size_t pairs, size_t max_block_size, size_t max_len) {
+        device = dev;
+        I = inputs;
+        O = outputs;
+        N = pairs;
+        ir_len = max_len;
+        B = next_pow2(max_block_size);                             // :115
+        log2b = ilog2(B);
+        if (B < 32 || B > 8192)
+            return fail(FFTCONV_E_UNSUPPORTED, "matrix block size " + std::to_string(B) + " outside 32..8192");
+        S = ceil_div(ir_len, B);                                   // :117
+        if (S * B > (size_t)INT32_MAX || I * std::max<size_t>(S, 1) > (size_t)INT32_MAX ||
+            N * std::max<size_t>(S, 1) > (size_t)INT32_MAX)
+            return fail(FFTCONV_E_UNSUPPORTED, "geometry exceeds 32-bit indexing");
+        act = S;
+        PTmax = total_parts(S);
+        if (I + PTmax > (size_t)INT32_MAX) return fail(FFTCONV_E_UNSUPPORTED, "geometry exceeds 32-bit indexing");
+        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        if (int r = H.alloc(N * S * B)) return r;
+        if (int r = X.alloc(I * S * B)) return r;
+        if (int r = pre.alloc(O * B)) return r;
+        if (int r = part.alloc(PTmax * B)) return r;               // (P_o is largest at active = S)
+        if (int r = ovl.alloc(O * B)) return r;
+        if (int r = ib.alloc(I * B)) return r;
+        if (int r = tw.alloc(2 * B)) return r;
+        if (int r = d_rowptr.alloc(O + 1)) return r;
+        if (int r = d_col.alloc(N)) return r;
+        if (int r = plan.alloc(O + 1)) return r;
+        if (int r = wg.alloc(PTmax)) return r;
+        if (int r = staging.alloc(N * ir_len)) return r;           // update() never allocates
+        if (int r = hstage.alloc(N * ir_len, ir_len)) return r;
+        std::vector<float2> t(2 * B);
+        const size_t NN = 2 * B;
+        for (size_t k = 0; k < NN; ++k) {
+            const double ang = -2.0 * M_PI * (double)k / (double)NN;
+            t[k] = make_float2((float)std::cos(ang), (float)std::sin(ang));
+        }
+        HIP_TRY(hipMemcpy(tw.p, t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_rowptr.p, rowptr.data(), d_rowptr.bytes(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_col.p, col.data(), d_col.bytes(), hipMemcpyHostToDevice));
+        return FFTCONV_OK;
+    }
+
+    // the IR transform of every listed pair from device samples (pair n at src
+    // + n * stride): rows at or past ceil(len_active / B) are zeroed (:210-212)
+    int ir_from_device(const float *src, size_t stride, size_t len_data, size_t len_active, hipStream_t s) {
+        const size_t step = 32768;  // (grid.y of the transform)
+        for (size_t p0 = 0; p0 < N; p0 += step) {
+            IrArgs a{};
+            a.H = H.p;
+            a.src = src + p0 * stride;
+            a.src_stride = (long long)stride;
+            a.len_data = (long long)len_data;
+            a.len_active = (long long)len_active;
+            a.tw = tw.p;
+            a.S = (int)S;
+            a.chan0 = (int)p0;
+            a.update_state = 0;
+            HIP_TRY(launch_ir_segments(log2b, a, (int)std::min(step, N - p0), s));
+        }
+        return FFTCONV_OK;
+    }
+
+    int zero_state(hipStream_t s) {  // :296-306
+        if (X.n) HIP_TRY(hipMemsetAsync(X.p, 0, X.bytes(), s));
+        if (ovl.n) HIP_TRY(hipMemsetAsync(ovl.p, 0, ovl.bytes(), s));
+        if (ib.n) HIP_TRY(hipMemsetAsync(ib.p, 0, ib.bytes(), s));
+        if (pre.n) HIP_TRY(hipMemsetAsync(pre.p, 0, pre.bytes(), s));
+        cur = 0;
+        fill = 0;
+        return FFTCONV_OK;
+    }
+
+    int init(int dev, size_t inputs, size_t outputs, size_t pairs, const uint32_t *po, const uint32_t *pi,
+             const float *responses, size_t len, size_t stride, size_t max_block, size_t max_len) {
+        if (int r = check_pattern(inputs, outputs, pairs, po, pi)) return r;
+        if (max_len < len)                                          // :106-110
+            return fail(FFTCONV_E_INVALID,
+                        "max_response_length must be at least the length of the initial impulse response");
+        if (int r = check_device(dev)) return r;
+        rowptr.assign(outputs + 1, 0);
+        col.resize(pairs);
+        for (size_t n = 0; n < pairs; ++n) {
+            ++rowptr[po[n] + 1];
+            col[n] = (int)pi[n];
+        }
+        for (size_t o = 0; o < outputs; ++o) rowptr[o + 1] += rowptr[o];
+        DeviceGuard g(dev);
+        if (int r = alloc_geometry(dev, inputs, outputs, pairs, max_block, max_len)) return r;
+        if (int r = zero_state(stream)) return r;
+        if (int r = rebuild_plan(stream)) return r;
+        if (S > 0) {
+            const bool shared = stride == 0 && N > 1;
+            if (len)
+                if (int r = hstage.upload(responses, shared ? 1 : N, len, stride, staging.p, ir_len, stream)) return r;
+            if (int r = ir_from_device(staging.p, shared ? 0 : ir_len, len, ir_len, stream)) return r;
+        }
+        HIP_TRY(hipStreamSynchronize(stream));
+        return FFTCONV_OK;
+    }
+
+    // FFTConvolver::update (:174-213) of every instance; (the caller has
+    // ordered s behind the handle's previous work)
+    int update_device(const float *src, size_t stride, size_t len, hipStream_t s) {
+        if (len > ir_len) return fail(FFTCONV_E_INVALID, "New impulse response is longer than initialized length");
+        if (ir_len == 0) return FFTCONV_OK;                         // :181-183
+        if (pre.n) HIP_TRY(hipMemsetAsync(pre.p, 0, pre.bytes(), s));   // :187
+        if (ovl.n) HIP_TRY(hipMemsetAsync(ovl.p, 0, ovl.bytes(), s));   // :188
+        act = ceil_div(len, B);                                     // :190 (current untouched)
+        if (int r = rebuild_plan(s)) return r;
+        return ir_from_device(src, stride, len, len, s);
+    }
+    int update_host(const float *src, size_t len, size_t stride) {
+        if (len > ir_len) return fail(FFTCONV_E_INVALID, "New impulse response is longer than initialized length");
+        if (ir_len == 0) return FFTCONV_OK;
+        DeviceGuard g(device);
+        if (int r = order.enter(stream)) return r;
+        const bool shared = stride == 0 && N > 1;
+        if (len)
+            if (int r = hstage.upload(src, shared ? 1 : N, len, stride, staging.p, ir_len, stream)) return r;
+        return update_device(staging.p, shared ? 0 : ir_len, len, stream);
+    }
+
+    int process_device(const float *din, size_t is, float *dout, size_t os, size_t n, hipStream_t s) {
+        if (n > (size_t)INT32_MAX) return fail(FFTCONV_E_UNSUPPORTED, "process length exceeds 2^31-1");
+        if (n == 0) return FFTCONV_OK;
+        if (act == 0) {  // :216-219 -- zero output, state untouched
+            HIP_TRY(hipMemset2DAsync(dout, os * sizeof(float), 0, n * sizeof(float), O, s));
+            return FFTCONV_OK;
+        }
+        MatrixSpArgs a{};
+        MatrixArgs &m = a.m;
+        m.H = H.p; m.X = X.p; m.ovl = ovl.p; m.ib = ib.p; m.pre = pre.p; m.part = part.p; m.tw = tw.p;
+        m.in_stride = (long long)is;
+        m.out_stride = (long long)os;
+        m.I = (int)I; m.O = (int)O; m.S = (int)S;
+        m.act = (int)act;
+        m.nt_h = Variant::current().nt_matrix(H.bytes()) ? 1 : 0;
+        a.rowptr = d_rowptr.p; a.col = d_col.p; a.plan = plan.p; a.wg = wg.p;
+        a.N = (int)N;
+        a.PT = (int)PT;
+        size_t processed = 0;
+        while (processed < n) {                                     // :222-294
+            const size_t k = std::min(n - processed, B - fill);     // :224-227
+            m.in = din + processed;
+            m.out = dout + processed;
+            m.cur = (int)cur;
+            m.fill = (int)fill;
+            m.k = (int)k;
+            HIP_TRY(launch_matrix_sp_chunk(log2b, a, s));
+            fill += k;
+            if (fill == B) {                                        // :277-291
+                fill = 0;
+                cur = cur > 0 ? cur - 1 : act - 1;
+            }
+            processed += k;
+        }
+        return FFTCONV_OK;
+    }
+
+    int process_device_steps(const float *din, size_t is, size_t in_step, float *dout, size_t os, size_t out_step,
+                             size_t n, size_t steps, hipStream_t s) {
+        for (size_t k = 0; k < steps; ++k)
+            if (int r = process_device(din + k * in_step, is, dout + k * out_step, os, n, s)) return r;
+        return FFTCONV_OK;
+    }
+
+    int process_host(const float *in, size_t in_len, float *out, size_t out_len) {
+        if (in_len < out_len) return fail(FFTCONV_E_INVALID, "input slice shorter than output (range end index out of range)");
+        if (out_len == 0) return FFTCONV_OK;
+        DeviceGuard g(device);
+        if (int r = order.enter(stream)) return r;
+        if (int r = scratch.ensure(I * out_len, O * out_len)) return r;
+        HIP_TRY(hipMemcpy2DAsync(scratch.in.p, out_len * sizeof(float), in, in_len * sizeof(float),
+                                 out_len * sizeof(float), I, hipMemcpyHostToDevice, stream));
+        if (int r = process_device(scratch.in.p, out_len, scratch.out.p, out_len, out_len, stream)) return r;
+        HIP_TRY(hipMemcpyAsync(out, scratch.out.p, O * out_len * sizeof(float), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return FFTCONV_OK;
+    }
+
+    int clone_from(const SparseMatrixCore &o) {  // #[derive(Clone)]
+        DeviceGuard g(o.device);
+        if (int r = o.order.drain(o.stream)) return r;
+        device = o.device;
+        I = o.I; O = o.O; N = o.N; ir_len = o.ir_len; B = o.B; log2b = o.log2b; S = o.S;
+        PTmax = o.PTmax; PT = o.PT;
+        cur = o.cur; act = o.act; fill = o.fill;
+        rowptr = o.rowptr;
+        col = o.col;
+        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        auto cp = [&](auto &dst, const auto &src) -> int {
+            if (int r = dst.alloc(src.n)) return r;
+            if (src.n) HIP_TRY(hipMemcpyAsync(dst.p, src.p, src.bytes(), hipMemcpyDeviceToDevice, stream));
+            return FFTCONV_OK;
+        };
+        if (int r = cp(H, o.H)) return r;
+        if (int r = cp(X, o.X)) return r;
+        if (int r = cp(pre, o.pre)) return r;
+        if (int r = cp(tw, o.tw)) return r;
+        if (int r = cp(ovl, o.ovl)) return r;
+        if (int r = cp(ib, o.ib)) return r;
+        if (int r = cp(d_rowptr, o.d_rowptr)) return r;
+        if (int r = cp(d_col, o.d_col)) return r;
+        if (int r = cp(plan, o.plan)) return r;
+        if (int r = cp(wg, o.wg)) return r;
+        if (int r = part.alloc(o.part.n)) return r;  // (rewritten by every block before it is read)
+        if (int r = staging.alloc(o.staging.n)) return r;
+        if (int r = hstage.alloc(o.hstage.n, ir_len)) return r;
+        HIP_TRY(hipStreamSynchronize(stream));
+        return FFTCONV_OK;
+    }
+};
+
+// ---------------------------------------------------------------------------
 // MatrixCrossfadeCore -- I x O CrossfadeConvolver<FFTConvolver> instances
 // (o, i) in lockstep: two MatrixCores A and B on the handle's
 // stream, ONE Crossfader and one response_pending for all of them, the mix
@@ -2945,6 +3226,7 @@ struct fftconv_uniform { UniformCore core; };
 struct fftconv_twostage { TwoStageCore core; };
 struct fftconv_crossfade { CrossfadeCore core; };
 struct fftconv_matrix { MatrixCore core; };
+struct fftconv_matrix_sparse { SparseMatrixCore core; };
 struct fftconv_matrix_crossfade { MatrixCrossfadeCore core; };
 struct fftconv_matrix_twostage { MatrixTwoStageCore core; };
 
@@ -3361,6 +3643,88 @@ size_t fftconv_matrix_block_size(const fftconv_matrix *h) { return h ? h->core.B
 size_t fftconv_matrix_seg_count(const fftconv_matrix *h) { return h ? h->core.S : 0; }
 int fftconv_matrix_mac_parts(const fftconv_matrix *h) { return h ? h->core.mac_parts() : 0; }
 int fftconv_matrix_state(const fftconv_matrix *h, size_t out3[3]) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    out3[0] = h->core.cur; out3[1] = h->core.act; out3[2] = h->core.fill;
+    return FFTCONV_OK;
+}
+
+// ---- sparse matrix ----------------------------------------------
+fftconv_matrix_sparse *fftconv_matrix_sparse_init(int device, size_t inputs, size_t outputs, size_t pairs,
+                                                  const uint32_t *pair_out, const uint32_t *pair_in,
+                                                  const float *responses, size_t response_len,
+                                                  size_t response_stride, size_t max_block_size,
+                                                  size_t max_response_length) {
+    set_error("");
+    auto *h = new (std::nothrow) fftconv_matrix_sparse();
+    if (!h) { set_error("out of host memory"); return nullptr; }
+    int r = h->core.init(device, inputs, outputs, pairs, pair_out, pair_in, responses, response_len, response_stride,
+                         max_block_size, max_response_length);
+    return make_or_null(r, h);
+}
+int fftconv_matrix_sparse_update(fftconv_matrix_sparse *h, const float *responses, size_t response_len,
+                                 size_t response_stride) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.update_host(responses, response_len, response_stride);
+}
+int fftconv_matrix_sparse_update_device(fftconv_matrix_sparse *h, const float *d_responses, size_t response_len,
+                                        size_t response_stride, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.device);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int r = h->core.order.enter(s)) return r;
+    return h->core.update_device(d_responses, response_stride, response_len, s);
+}
+int fftconv_matrix_sparse_reset(fftconv_matrix_sparse *h) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.device);
+    if (int r = h->core.order.enter(h->core.stream)) return r;
+    if (int r = h->core.zero_state(h->core.stream)) return r;
+    HIP_TRY(hipStreamSynchronize(h->core.stream));
+    return FFTCONV_OK;
+}
+int fftconv_matrix_sparse_process(fftconv_matrix_sparse *h, const float *input, size_t input_len, float *output,
+                                  size_t output_len) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.process_host(input, input_len, output, output_len);
+}
+int fftconv_matrix_sparse_process_device(fftconv_matrix_sparse *h, const float *d_input, size_t in_stride,
+                                         float *d_output, size_t out_stride, size_t len, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.device);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int r = h->core.order.enter(s)) return r;
+    return h->core.process_device(d_input, in_stride, d_output, out_stride, len, s);
+}
+int fftconv_matrix_sparse_process_device_steps(fftconv_matrix_sparse *h, const float *d_input, size_t in_stride,
+                                               size_t in_step, float *d_output, size_t out_stride, size_t out_step,
+                                               size_t len, size_t steps, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.device);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int r = h->core.order.enter(s)) return r;
+    return h->core.process_device_steps(d_input, in_stride, in_step, d_output, out_stride, out_step, len, steps, s);
+}
+fftconv_matrix_sparse *fftconv_matrix_sparse_clone(const fftconv_matrix_sparse *h) {
+    if (!h) { set_error("null handle"); return nullptr; }
+    auto *c = new (std::nothrow) fftconv_matrix_sparse();
+    if (!c) { set_error("out of host memory"); return nullptr; }
+    return make_or_null(c->core.clone_from(h->core), c);
+}
+void fftconv_matrix_sparse_destroy(fftconv_matrix_sparse *h) { delete h; }
+int fftconv_matrix_sparse_synchronize(fftconv_matrix_sparse *h) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.device);
+    return h->core.order.drain(h->core.stream);
+}
+size_t fftconv_matrix_sparse_inputs(const fftconv_matrix_sparse *h) { return h ? h->core.I : 0; }
+size_t fftconv_matrix_sparse_outputs(const fftconv_matrix_sparse *h) { return h ? h->core.O : 0; }
+size_t fftconv_matrix_sparse_pairs(const fftconv_matrix_sparse *h) { return h ? h->core.N : 0; }
+size_t fftconv_matrix_sparse_block_size(const fftconv_matrix_sparse *h) { return h ? h->core.B : 0; }
+size_t fftconv_matrix_sparse_seg_count(const fftconv_matrix_sparse *h) { return h ? h->core.S : 0; }
+int fftconv_matrix_sparse_output_parts(const fftconv_matrix_sparse *h, size_t output) {
+    return h && output < h->core.O ? h->core.output_parts(output) : 0;
+}
+int fftconv_matrix_sparse_state(const fftconv_matrix_sparse *h, size_t out3[3]) {
     if (!h) return fail(FFTCONV_E_INVALID, "null handle");
     out3[0] = h->core.cur; out3[1] = h->core.act; out3[2] = h->core.fill;
     return FFTCONV_OK;

@@ -403,9 +403,34 @@ struct MatrixArgs {
 };
 // P for a geometry and its active segments: a function of these only
 int matrix_mac_parts(int inputs, int log2b, int seg_count, int active);
+// the rule itself -- about 64 rows per part, at most 64 parts -- for the host
+// and for the sparse matrix's plan kernel (matrix_sp.hip): one definition
+__host__ __device__ inline int matrix_parts_rule(long long inputs, int active) {
+    const long long R = inputs * (active > 1 ? active - 1 : 0);
+    const long long p = (R + 63) / 64;
+    return (int)(p < 1 ? 1 : (p > 64 ? 64 : p));
+}
 // the chunk's two launches (32 <= B <= 8192): A = R2C of every input + the
 // split-row MAC when the chunk starts a block, B = the outputs' finish
 hipError_t launch_matrix_chunk(int log2b, const MatrixArgs &a, hipStream_t s);
+
+// SparseMatrixConvolver (matrix_sp.hip): one chunk of a matrix
+// that holds only its N listed (output, input) pairs, in CSR order.  `m` is the
+// dense chunk with H = [N][S][B] (pair n = row n) and part = [sum P_o][B];
+// m.P and m.rpp are unused -- every output has its own, from the plan.
+struct MatrixSpArgs {
+    MatrixArgs m;
+    const int *rowptr;     // [O + 1] pairs of output o = [rowptr[o], rowptr[o + 1])
+    const int *col;        // [N] input of pair n
+    const int *plan;       // [O + 1] prefix sums of P_o = matrix_parts_rule(k_o, act)
+    const int4 *wg;        // [PT] MAC workgroup m = plan[o] + p: {rowptr[o], k_o, p, P_o}
+    int N;                 // pairs
+    int PT;                // plan[O]: the MAC workgroups of launch A, rows of `part`
+};
+// plan[0..O] and wg[0..plan[O]) for `act` active segments, one workgroup on s
+hipError_t launch_matrix_sp_plan(const int *rowptr, int *plan, int4 *wg, int O, int act, hipStream_t s);
+// the chunk's two launches (32 <= B <= 8192)
+hipError_t launch_matrix_sp_chunk(int log2b, const MatrixSpArgs &a, hipStream_t s);
 
 // MatrixCrossfadeConvolver (matrix_xf.hip): one chunk of the two
 // matrices A and B of a crossfaded handle while they are in step (equal

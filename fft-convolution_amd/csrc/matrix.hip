@@ -134,9 +134,7 @@ hipError_t launch_matrix_t(const MatrixArgs &a, hipStream_t s) {
 int matrix_mac_parts(int inputs, int log2b, int seg_count, int active) {
     (void)log2b;
     (void)seg_count;
-    const long long R = (long long)inputs * (active > 1 ? active - 1 : 0);
-    const long long p = (R + 63) / 64;
-    return (int)(p < 1 ? 1 : (p > 64 ? 64 : p));
+    return matrix_parts_rule(inputs, active);
 }
 
 hipError_t launch_matrix_chunk(int log2b, const MatrixArgs &a, hipStream_t s) {

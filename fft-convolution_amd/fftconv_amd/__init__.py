@@ -37,6 +37,7 @@ FFTCONV_E_NOMEM = -5
 
 # every symbol include/fftconv.h declares: name -> (restype, argtypes)
 _vp, _sz, _fp, _i = C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.c_int
+_u32p = C.POINTER(C.c_uint32)
 SIGNATURES = {
     "fftconv_abi_version": (_i, []),
     "fftconv_last_error": (C.c_char_p, []),
@@ -118,6 +119,23 @@ SIGNATURES = {
     "fftconv_matrix_seg_count": (_sz, [_vp]),
     "fftconv_matrix_mac_parts": (_i, [_vp]),
     "fftconv_matrix_state": (_i, [_vp, C.POINTER(_sz)]),
+    "fftconv_matrix_sparse_init": (_vp, [_i, _sz, _sz, _sz, _u32p, _u32p, _fp, _sz, _sz, _sz, _sz]),
+    "fftconv_matrix_sparse_update": (_i, [_vp, _fp, _sz, _sz]),
+    "fftconv_matrix_sparse_update_device": (_i, [_vp, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_sparse_reset": (_i, [_vp]),
+    "fftconv_matrix_sparse_process": (_i, [_vp, _fp, _sz, _fp, _sz]),
+    "fftconv_matrix_sparse_process_device": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_sparse_process_device_steps": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _sz, _sz, _vp]),
+    "fftconv_matrix_sparse_clone": (_vp, [_vp]),
+    "fftconv_matrix_sparse_destroy": (None, [_vp]),
+    "fftconv_matrix_sparse_synchronize": (_i, [_vp]),
+    "fftconv_matrix_sparse_inputs": (_sz, [_vp]),
+    "fftconv_matrix_sparse_outputs": (_sz, [_vp]),
+    "fftconv_matrix_sparse_pairs": (_sz, [_vp]),
+    "fftconv_matrix_sparse_block_size": (_sz, [_vp]),
+    "fftconv_matrix_sparse_seg_count": (_sz, [_vp]),
+    "fftconv_matrix_sparse_output_parts": (_i, [_vp, _sz]),
+    "fftconv_matrix_sparse_state": (_i, [_vp, C.POINTER(_sz)]),
     "fftconv_matrix_crossfade_init": (_vp, [_i, _sz, _sz, _fp, _sz, _sz, _sz, _sz]),
     "fftconv_matrix_crossfade_new": (_vp, [_vp, _sz, _sz, _sz]),
     "fftconv_matrix_crossfade_update": (_i, [_vp, _fp, _sz, _sz]),
@@ -211,7 +229,7 @@ def _check(rc: int):
 def _handle(h):
     if not h:
         msg = last_error()
-        if "max_response_length" in msg or "longer" in msg or "at least one input" in msg:
+        if "max_response_length" in msg or "longer" in msg or "at least one input" in msg or "pair" in msg:
             raise ConvolutionPanic(msg)
         raise DeviceError(msg or "handle creation failed")
     return h
@@ -616,6 +634,94 @@ class MatrixConvolver(_Base):
         return tuple(int(v) for v in out)
 
 
+class SparseMatrixConvolver(_Base):
+    """Matrix convolution over a listed pair set (fftconv.h,
+    "SparseMatrixConvolver"): one FFTConvolver instance per listed (output,
+    input) pair, in lockstep; output o is the sum of the instances listed for
+    it, an output without pairs is zero.  Only the listed pairs are stored,
+    uploaded and streamed."""
+
+    _prefix = "matrix_sparse"
+
+    def __init__(self, h, inputs: int, outputs: int, pairs: int):
+        super().__init__(h, inputs)
+        self.inputs = inputs
+        self.outputs = outputs
+        self.pairs = pairs
+
+    def _rows(self, responses):
+        r = _f32(responses)
+        if r.ndim != 2 or r.shape[0] != self.pairs:
+            raise ValueError("responses must be [pairs][len]")
+        return r
+
+    @classmethod
+    def init(cls, pairs, responses, inputs: int, outputs: int, max_block_size: int, max_response_length: int,
+             device: int = 0):
+        """pairs: (output, input) tuples, strictly ascending; responses[n] is
+        the response of pairs[n]."""
+        pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
+        if pr.size and (pr.min() < 0 or pr.max() >= 1 << 32):
+            raise ValueError("pair indices must fit 32 unsigned bits")
+        po = np.ascontiguousarray(pr[:, 0].astype(np.uint32))
+        pi = np.ascontiguousarray(pr[:, 1].astype(np.uint32))
+        r = _f32(responses)
+        if r.ndim != 2 or r.shape[0] != len(pr):
+            raise ValueError("responses must be [pairs][len]")
+        n = r.shape[1]
+        h = lib().fftconv_matrix_sparse_init(device, inputs, outputs, len(pr), po.ctypes.data_as(_u32p),
+                                             pi.ctypes.data_as(_u32p), _p(r), n, n, max_block_size,
+                                             max_response_length)
+        return cls(_handle(h), inputs, outputs, len(pr))
+
+    def update(self, responses):
+        """update() of every listed pair with responses[pairs][len] (whole matrix only)."""
+        r = self._rows(responses)
+        _check(lib().fftconv_matrix_sparse_update(self._h, _p(r), r.shape[1], r.shape[1]))
+
+    def update_device(self, d_responses: int, response_len: int, stride: int = 0, stream: int = 0):
+        """update() from device memory (pair n, in list order, at d_responses +
+        4 * n * stride; stride 0 = one response for every pair), stream-ordered."""
+        _check(self._fn("update_device")(self._h, C.c_void_p(d_responses), response_len, stride,
+                                         C.c_void_p(stream) if stream else None))
+
+    def reset(self):
+        _check(lib().fftconv_matrix_sparse_reset(self._h))
+
+    def process(self, inp, out_len: int | None = None) -> np.ndarray:
+        """x[inputs][n] -> y[outputs][out_len or n]."""
+        x = _f32(inp)
+        if x.ndim != 2 or x.shape[0] != self.inputs:
+            raise ValueError(f"input must be [{self.inputs}][n]")
+        n_in = x.shape[1]
+        n = n_in if out_len is None else out_len
+        y = np.zeros((self.outputs, n), np.float32)
+        _check(lib().fftconv_matrix_sparse_process(self._h, _p(x), n_in, _p(y), n))
+        return y
+
+    def clone(self):
+        return SparseMatrixConvolver(_handle(lib().fftconv_matrix_sparse_clone(self._h)), self.inputs, self.outputs,
+                                     self.pairs)
+
+    @property
+    def block_size(self) -> int:
+        return int(lib().fftconv_matrix_sparse_block_size(self._h))
+
+    @property
+    def seg_count(self) -> int:
+        return int(lib().fftconv_matrix_sparse_seg_count(self._h))
+
+    def output_parts(self, o: int) -> int:
+        """P_o: workgroups sharing output o's spectral sum, for the current active_seg_count."""
+        return int(lib().fftconv_matrix_sparse_output_parts(self._h, o))
+
+    def state(self):
+        """(current, active_seg_count, input_buffer_fill) of the whole matrix."""
+        out = (C.c_size_t * 3)()
+        _check(lib().fftconv_matrix_sparse_state(self._h, out))
+        return tuple(int(v) for v in out)
+
+
 class MatrixCrossfadeConvolver(_Base):
     """Crossfaded response switching for the matrix (fftconv.h,
     "MatrixCrossfadeConvolver"): inputs x outputs CrossfadeConvolver<FFTConvolver>
@@ -749,7 +855,7 @@ class MatrixTwoStageConvolver(_Base):
 
 __all__ = [
     "Fft", "FFTConvolver", "TwoStageFFTConvolver", "CrossfadeConvolver", "MatrixConvolver",
-    "MatrixCrossfadeConvolver", "MatrixTwoStageConvolver", "ConvolutionPanic",
+    "SparseMatrixConvolver", "MatrixCrossfadeConvolver", "MatrixTwoStageConvolver", "ConvolutionPanic",
     "NotImplementedInReference", "DeviceError", "complex_size", "compute_tail_block_size", "device_count",
     "lib", "LIB_PATH", "SIGNATURES",
 ]

@@ -41,6 +41,7 @@
 #define FFTCONV_H
 
 #include <stddef.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -61,6 +62,7 @@ typedef struct fftconv_uniform fftconv_uniform;     /* FFTConvolver        src/f
 typedef struct fftconv_twostage fftconv_twostage;   /* TwoStageFFTConvolver src/fft_convolver.rs:323-512 */
 typedef struct fftconv_crossfade fftconv_crossfade; /* CrossfadeConvolver<FFTConvolver | TwoStageFFTConvolver> src/crossfade_convolver.rs:10-105 */
 typedef struct fftconv_matrix fftconv_matrix;       /* inputs x outputs FFTConvolver instances, summed per output (below) */
+typedef struct fftconv_matrix_sparse fftconv_matrix_sparse; /* one FFTConvolver instance per listed (output, input) pair (below) */
 typedef struct fftconv_matrix_crossfade fftconv_matrix_crossfade; /* inputs x outputs CrossfadeConvolver<FFTConvolver> instances (below) */
 typedef struct fftconv_matrix_twostage fftconv_matrix_twostage;   /* inputs x outputs TwoStageFFTConvolver instances (below) */
 
@@ -385,6 +387,87 @@ size_t fftconv_matrix_seg_count(const fftconv_matrix *h);
 int fftconv_matrix_mac_parts(const fftconv_matrix *h);
 /* {current, active_seg_count, input_buffer_fill} as of the calls enqueued so far */
 int fftconv_matrix_state(const fftconv_matrix *h, size_t out3[3]);
+
+/* ---- SparseMatrixConvolver: matrix convolution over a listed pair set ----
+ *     y[o] = sum over the listed pairs (o, i) of x[i] * h[(o, i)]
+ * A sparse matrix has I inputs, O outputs and N >= 1 pairs (o_n, i_n), strictly
+ * ascending in (o, i): sorted, no duplicates.  It behaves as N FFTConvolver
+ * instances (src/fft_convolver.rs:86-307), one per listed pair, all created,
+ * updated and reset together with the same response_len: instance n processes
+ * input i_n, output o is the sum of the instances listed for it.  An output
+ * with no listed pair is 0.0 for every sample of every call; an input that no
+ * pair reads is accepted and ignored.  One {current, active_seg_count,
+ * input_buffer_fill} describes the handle (fftconv_matrix_sparse_state).  The
+ * pattern is fixed for the life of the handle; update replaces the N responses.
+ * Only the listed pairs are stored, uploaded, transformed and streamed.
+ * The dense matrix's two departures carry over unchanged: non-finite samples
+ * are outside the parity contract, and only whole-matrix update is offered.
+ * Responses: pair n, in list order, at responses + n * response_stride
+ * (response_stride 0 = one response for every pair).
+ * Order of summation (part of the contract), the dense matrix's with an
+ * output's pair list in place of 0..I-1; k_o = the pairs of output o:
+ *  - the rows of output o are H[pair e][s] (.) X[i_e][(current + s) % active],
+ *    s >= 1, pair e = the e-th entry of output o's list and i_e its input,
+ *    flattened pair-major in list order: r = e * (active - 1) + s - 1;
+ *  - output o has P_o parts (fftconv_matrix_sparse_output_parts): the rule of
+ *    fftconv_matrix_mac_parts with inputs := k_o, a function of output o's own
+ *    list and active_seg_count only;
+ *  - the split into parts and row groups, the order inside a group, of the
+ *    groups and of the parts are the dense matrix's;
+ *  - the finishing launch adds the row-0 terms X[i_e][current] (.) H[pair e][0]
+ *    in ascending e.
+ * So (1) output o is bit-identical to the single output of a dense
+ * fftconv_matrix with k_o inputs that holds the responses h[pair e] and is fed
+ * x[i_e] in list order, and (2) an output's bits depend on nothing outside its
+ * own pair list and the inputs it names: a pattern split by outputs over
+ * several handles (or GPUs) computes bit-identical rows.
+ * Errors: pairs == 0, inputs == 0, outputs == 0, a pair index out of range, a
+ * pair list that is not strictly ascending, or response_len >
+ * max_response_length is FFTCONV_E_INVALID; a block outside 32..8192
+ * (next_power_of_two(max_block_size)) or indices past 32 bits is
+ * FFTCONV_E_UNSUPPORTED; init returns NULL on error (fftconv_last_error).
+ * Out of scope: a sparse crossfade and a sparse two-stage matrix (those take a
+ * dense fftconv_matrix), changing the pattern after init, and any lookahead
+ * for matrices. */
+fftconv_matrix_sparse *fftconv_matrix_sparse_init(int device, size_t inputs, size_t outputs, size_t pairs,
+                                                  const uint32_t *pair_out, const uint32_t *pair_in,
+                                                  const float *responses, size_t response_len,
+                                                  size_t response_stride, size_t max_block_size,
+                                                  size_t max_response_length);
+/* :174-213 for every listed pair; asynchronous like fftconv_uniform_update: no
+ * allocation, no host wait.  active_seg_count = ceil(response_len / block),
+ * current is left alone (:186-190). */
+int fftconv_matrix_sparse_update(fftconv_matrix_sparse *h, const float *responses, size_t response_len,
+                                 size_t response_stride);
+int fftconv_matrix_sparse_update_device(fftconv_matrix_sparse *h, const float *d_responses, size_t response_len,
+                                        size_t response_stride, void *hip_stream);
+int fftconv_matrix_sparse_reset(fftconv_matrix_sparse *h); /* :296-306 */
+/* input [inputs][input_len], output [outputs][output_len], host memory;
+ * input_len < output_len is FFTCONV_E_INVALID. */
+int fftconv_matrix_sparse_process(fftconv_matrix_sparse *h, const float *input, size_t input_len, float *output,
+                                  size_t output_len);
+/* device memory, stream-ordered: input i at d_input + i * in_stride, output o
+ * at d_output + o * out_stride (strides in floats). */
+int fftconv_matrix_sparse_process_device(fftconv_matrix_sparse *h, const float *d_input, size_t in_stride,
+                                         float *d_output, size_t out_stride, size_t len, void *hip_stream);
+/* `steps` consecutive process_device calls, call k at d_input + k * in_step /
+ * d_output + k * out_step; the same bits as the separate calls. */
+int fftconv_matrix_sparse_process_device_steps(fftconv_matrix_sparse *h, const float *d_input, size_t in_stride,
+                                               size_t in_step, float *d_output, size_t out_stride, size_t out_step,
+                                               size_t len, size_t steps, void *hip_stream);
+fftconv_matrix_sparse *fftconv_matrix_sparse_clone(const fftconv_matrix_sparse *h);
+void fftconv_matrix_sparse_destroy(fftconv_matrix_sparse *h);
+int fftconv_matrix_sparse_synchronize(fftconv_matrix_sparse *h);
+size_t fftconv_matrix_sparse_inputs(const fftconv_matrix_sparse *h);
+size_t fftconv_matrix_sparse_outputs(const fftconv_matrix_sparse *h);
+size_t fftconv_matrix_sparse_pairs(const fftconv_matrix_sparse *h);
+size_t fftconv_matrix_sparse_block_size(const fftconv_matrix_sparse *h);
+size_t fftconv_matrix_sparse_seg_count(const fftconv_matrix_sparse *h);
+/* P_o: the workgroups that share output `output`'s spectral sum, for the
+ * current active_seg_count (1 for an output without pairs; 0 for a bad index) */
+int fftconv_matrix_sparse_output_parts(const fftconv_matrix_sparse *h, size_t output);
+/* {current, active_seg_count, input_buffer_fill} as of the calls enqueued so far */
+int fftconv_matrix_sparse_state(const fftconv_matrix_sparse *h, size_t out3[3]);
 
 /* ---- MatrixCrossfadeConvolver: crossfaded response switching for the matrix ----
  * A matrix crossfade (inputs I, outputs O) behaves as I*O reference
