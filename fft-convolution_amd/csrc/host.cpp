@@ -2087,6 +2087,151 @@ struct MatrixCore {
 };
 
 // ---------------------------------------------------------------------------
+// MatrixLookaheadCore -- the MatrixCore's I x O instances with one level of
+// far-row windows (matrix_la.hip).  The dense core `m` owns the
+// geometry, the buffers, the stream and {current, active, fill}; this core adds
+// the near / far partial sums and the block count that schedules the anchors.
+//   t   blocks started since init (the block the next fill == 0 chunk starts)
+//   tv  windows anchored before block tv are invalid: init, reset, update and
+//       every block that starts with current >= active (or with the windows
+//       switched off) move it past every anchor made so far
+// ---------------------------------------------------------------------------
+struct MatrixLookaheadCore {
+    static constexpr size_t Q = kMatrixLaQ;
+    MatrixCore m;
+    DevPtr<float2> far;  // [O][Pf_max][Q][B]; the near partial sums use m.part (Pn <= the dense P)
+    long long t = 0, tv = 0;
+    bool windows = true;
+
+    // rows (i, s) of one output: near 1 <= s < min(Q, active), far Q <= s < active
+    size_t near_rows() const { return m.I * (std::min(m.act, Q) > 0 ? std::min(m.act, Q) - 1 : 0); }
+    size_t far_rows() const { return m.act > Q ? m.I * (m.act - Q) : 0; }
+    int near_parts() const { return matrix_la_parts((long long)near_rows()); }
+    int far_parts() const { return far_rows() ? matrix_la_parts((long long)far_rows()) : 0; }
+    // outputs that anchor when the next block starts
+    int anchors() const {
+        if (!windows || m.act <= Q || m.cur >= m.act) return 0;
+        const size_t t0 = (size_t)(t % (long long)Q);
+        return t0 < m.O ? (int)((m.O - t0 + Q - 1) / Q) : 0;
+    }
+
+    // no anchor made so far counts from here on; the block in progress (fill >
+    // 0) has made its anchors already, so they are past too
+    void invalidate() { tv = m.fill ? t + 1 : t; }
+
+    int alloc_extra() {
+        const size_t pf = m.S > Q ? (size_t)matrix_la_parts((long long)m.I * (long long)(m.S - Q)) : 0;
+        return far.alloc(m.O * pf * Q * m.B);
+    }
+
+    int init(int dev, size_t inputs, size_t outputs, const float *responses, size_t len, size_t stride,
+             size_t max_block, size_t max_len) {
+        if (inputs && outputs && max_len >= len && next_pow2(max_block) > ((size_t)1 << kMatrixLaMaxLog2B))
+            return fail(FFTCONV_E_UNSUPPORTED, "matrix lookahead block size " + std::to_string(next_pow2(max_block)) +
+                                                   " outside 32..512 (use the MatrixConvolver)");
+        if (int r = m.init(dev, inputs, outputs, responses, len, stride, max_block, max_len)) return r;
+        DeviceGuard g(dev);
+        t = tv = 0;
+        return alloc_extra();
+    }
+    int update_device(const float *src, size_t stride, size_t len, hipStream_t s) {
+        if (int r = m.update_device(src, stride, len, s)) return r;
+        invalidate();
+        return FFTCONV_OK;
+    }
+    int update_host(const float *src, size_t len, size_t stride) {
+        if (int r = m.update_host(src, len, stride)) return r;
+        invalidate();
+        return FFTCONV_OK;
+    }
+    int reset(hipStream_t s) {
+        if (m.fill) ++t;  // (the block in progress is dropped: its number is not used again)
+        if (int r = m.zero_state(s)) return r;
+        invalidate();
+        return FFTCONV_OK;
+    }
+
+    int process_device(const float *din, size_t is, float *dout, size_t os, size_t n, hipStream_t s) {
+        if (n > (size_t)INT32_MAX) return fail(FFTCONV_E_UNSUPPORTED, "process length exceeds 2^31-1");
+        if (n == 0) return FFTCONV_OK;
+        if (m.act == 0) {  // :216-219 -- zero output, state untouched
+            HIP_TRY(hipMemset2DAsync(dout, os * sizeof(float), 0, n * sizeof(float), m.O, s));
+            return FFTCONV_OK;
+        }
+        MatrixLaArgs la{};
+        MatrixArgs &a = la.m;
+        a.H = m.H.p; a.X = m.X.p; a.ovl = m.ovl.p; a.ib = m.ib.p; a.pre = m.pre.p; a.part = m.part.p; a.tw = m.tw.p;
+        a.in_stride = (long long)is;
+        a.out_stride = (long long)os;
+        a.I = (int)m.I; a.O = (int)m.O; a.S = (int)m.S;
+        a.P = near_parts();
+        a.rpp = (int)ceil_div(near_rows(), (size_t)a.P);
+        a.act = (int)m.act;
+        la.far = far.p;
+        la.Pf = far_parts();
+        la.rppf = la.Pf ? (int)ceil_div(far_rows(), (size_t)la.Pf) : 0;
+        // by the whole H, as the dense matrix: a block streams 1 / Q of the far
+        // rows, but over Q blocks all of H passes through the cache (measured,
+        // judging by a block's own bytes chose plain loads at M2 and lost 6 %)
+        a.nt_h = Variant::current().nt_matrix(m.H.bytes()) ? 1 : 0;
+        size_t processed = 0;
+        while (processed < n) {                                     // :222-294
+            const size_t k = std::min(n - processed, m.B - m.fill); // :224-227
+            if (m.fill == 0 && (!windows || m.cur >= m.act)) tv = t + 1;  // no anchor in this block
+            a.in = din + processed;
+            a.out = dout + processed;
+            a.cur = (int)m.cur;
+            a.fill = (int)m.fill;
+            a.k = (int)k;
+            la.t = t;
+            la.tv = tv;
+            HIP_TRY(launch_matrix_la_chunk(m.log2b, la, s));
+            m.fill += k;
+            if (m.fill == m.B) {                                    // :277-291
+                m.fill = 0;
+                m.cur = m.cur > 0 ? m.cur - 1 : m.act - 1;
+                ++t;
+            }
+            processed += k;
+        }
+        return FFTCONV_OK;
+    }
+
+    int process_device_steps(const float *din, size_t is, size_t in_step, float *dout, size_t os, size_t out_step,
+                             size_t n, size_t steps, hipStream_t s) {
+        for (size_t k = 0; k < steps; ++k)
+            if (int r = process_device(din + k * in_step, is, dout + k * out_step, os, n, s)) return r;
+        return FFTCONV_OK;
+    }
+
+    int process_host(const float *in, size_t in_len, float *out, size_t out_len) {
+        if (in_len < out_len) return fail(FFTCONV_E_INVALID, "input slice shorter than output (range end index out of range)");
+        if (out_len == 0) return FFTCONV_OK;
+        DeviceGuard g(m.device);
+        if (int r = m.order.enter(m.stream)) return r;
+        if (int r = m.scratch.ensure(m.I * out_len, m.O * out_len)) return r;
+        HIP_TRY(hipMemcpy2DAsync(m.scratch.in.p, out_len * sizeof(float), in, in_len * sizeof(float),
+                                 out_len * sizeof(float), m.I, hipMemcpyHostToDevice, m.stream));
+        if (int r = process_device(m.scratch.in.p, out_len, m.scratch.out.p, out_len, out_len, m.stream)) return r;
+        HIP_TRY(hipMemcpyAsync(out, m.scratch.out.p, m.O * out_len * sizeof(float), hipMemcpyDeviceToHost, m.stream));
+        HIP_TRY(hipStreamSynchronize(m.stream));
+        return FFTCONV_OK;
+    }
+
+    int clone_from(const MatrixLookaheadCore &o) {  // #[derive(Clone)]: the windows and {t, tv} too
+        if (int r = m.clone_from(o.m)) return r;
+        DeviceGuard g(m.device);
+        t = o.t;
+        tv = o.tv;
+        windows = o.windows;
+        if (int r = far.alloc(o.far.n)) return r;
+        if (far.n) HIP_TRY(hipMemcpyAsync(far.p, o.far.p, far.bytes(), hipMemcpyDeviceToDevice, m.stream));
+        HIP_TRY(hipStreamSynchronize(m.stream));
+        return FFTCONV_OK;
+    }
+};
+
+// ---------------------------------------------------------------------------
 // SparseMatrixCore -- N FFTConvolver instances in lockstep, one per listed
 // (output, input) pair: the MatrixCore's scheme over a CSR
 // pattern that is fixed for the life of the handle.  H, the staging and the
@@ -3227,6 +3372,7 @@ struct fftconv_twostage { TwoStageCore core; };
 struct fftconv_crossfade { CrossfadeCore core; };
 struct fftconv_matrix { MatrixCore core; };
 struct fftconv_matrix_sparse { SparseMatrixCore core; };
+struct fftconv_matrix_lookahead { MatrixLookaheadCore core; };
 struct fftconv_matrix_crossfade { MatrixCrossfadeCore core; };
 struct fftconv_matrix_twostage { MatrixTwoStageCore core; };
 
@@ -3647,6 +3793,92 @@ int fftconv_matrix_state(const fftconv_matrix *h, size_t out3[3]) {
     out3[0] = h->core.cur; out3[1] = h->core.act; out3[2] = h->core.fill;
     return FFTCONV_OK;
 }
+
+// ---- matrix with far-row windows ---------------------------------
+fftconv_matrix_lookahead *fftconv_matrix_lookahead_init(int device, size_t inputs, size_t outputs,
+                                                        const float *responses, size_t response_len,
+                                                        size_t response_stride, size_t max_block_size,
+                                                        size_t max_response_length) {
+    set_error("");
+    auto *h = new (std::nothrow) fftconv_matrix_lookahead();
+    if (!h) { set_error("out of host memory"); return nullptr; }
+    int r = h->core.init(device, inputs, outputs, responses, response_len, response_stride, max_block_size,
+                         max_response_length);
+    return make_or_null(r, h);
+}
+int fftconv_matrix_lookahead_update(fftconv_matrix_lookahead *h, const float *responses, size_t response_len,
+                                    size_t response_stride) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.update_host(responses, response_len, response_stride);
+}
+int fftconv_matrix_lookahead_update_device(fftconv_matrix_lookahead *h, const float *d_responses, size_t response_len,
+                                           size_t response_stride, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.m.device);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int r = h->core.m.order.enter(s)) return r;
+    return h->core.update_device(d_responses, response_stride, response_len, s);
+}
+int fftconv_matrix_lookahead_reset(fftconv_matrix_lookahead *h) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.m.device);
+    if (int r = h->core.m.order.enter(h->core.m.stream)) return r;
+    if (int r = h->core.reset(h->core.m.stream)) return r;
+    HIP_TRY(hipStreamSynchronize(h->core.m.stream));
+    return FFTCONV_OK;
+}
+int fftconv_matrix_lookahead_process(fftconv_matrix_lookahead *h, const float *input, size_t input_len, float *output,
+                                     size_t output_len) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.process_host(input, input_len, output, output_len);
+}
+int fftconv_matrix_lookahead_process_device(fftconv_matrix_lookahead *h, const float *d_input, size_t in_stride,
+                                            float *d_output, size_t out_stride, size_t len, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.m.device);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int r = h->core.m.order.enter(s)) return r;
+    return h->core.process_device(d_input, in_stride, d_output, out_stride, len, s);
+}
+int fftconv_matrix_lookahead_process_device_steps(fftconv_matrix_lookahead *h, const float *d_input, size_t in_stride,
+                                                  size_t in_step, float *d_output, size_t out_stride, size_t out_step,
+                                                  size_t len, size_t steps, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.m.device);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int r = h->core.m.order.enter(s)) return r;
+    return h->core.process_device_steps(d_input, in_stride, in_step, d_output, out_stride, out_step, len, steps, s);
+}
+fftconv_matrix_lookahead *fftconv_matrix_lookahead_clone(const fftconv_matrix_lookahead *h) {
+    if (!h) { set_error("null handle"); return nullptr; }
+    auto *c = new (std::nothrow) fftconv_matrix_lookahead();
+    if (!c) { set_error("out of host memory"); return nullptr; }
+    return make_or_null(c->core.clone_from(h->core), c);
+}
+void fftconv_matrix_lookahead_destroy(fftconv_matrix_lookahead *h) { delete h; }
+int fftconv_matrix_lookahead_synchronize(fftconv_matrix_lookahead *h) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.m.device);
+    return h->core.m.order.drain(h->core.m.stream);
+}
+size_t fftconv_matrix_lookahead_inputs(const fftconv_matrix_lookahead *h) { return h ? h->core.m.I : 0; }
+size_t fftconv_matrix_lookahead_outputs(const fftconv_matrix_lookahead *h) { return h ? h->core.m.O : 0; }
+size_t fftconv_matrix_lookahead_block_size(const fftconv_matrix_lookahead *h) { return h ? h->core.m.B : 0; }
+size_t fftconv_matrix_lookahead_seg_count(const fftconv_matrix_lookahead *h) { return h ? h->core.m.S : 0; }
+int fftconv_matrix_lookahead_state(const fftconv_matrix_lookahead *h, size_t out3[3]) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    out3[0] = h->core.m.cur; out3[1] = h->core.m.act; out3[2] = h->core.m.fill;
+    return FFTCONV_OK;
+}
+int fftconv_matrix_lookahead_period(void) { return kMatrixLaQ; }
+int fftconv_matrix_lookahead_near_parts(const fftconv_matrix_lookahead *h) { return h ? h->core.near_parts() : 0; }
+int fftconv_matrix_lookahead_far_parts(const fftconv_matrix_lookahead *h) { return h ? h->core.far_parts() : 0; }
+int fftconv_matrix_lookahead_set_windows(fftconv_matrix_lookahead *h, int on) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    h->core.windows = on != 0;
+    return FFTCONV_OK;
+}
+int fftconv_matrix_lookahead_anchors(const fftconv_matrix_lookahead *h) { return h ? h->core.anchors() : 0; }
 
 // ---- sparse matrix ----------------------------------------------
 fftconv_matrix_sparse *fftconv_matrix_sparse_init(int device, size_t inputs, size_t outputs, size_t pairs,

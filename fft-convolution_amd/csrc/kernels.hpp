@@ -432,6 +432,46 @@ hipError_t launch_matrix_sp_plan(const int *rowptr, int *plan, int4 *wg, int O, 
 // the chunk's two launches (32 <= B <= 8192)
 hipError_t launch_matrix_sp_chunk(int log2b, const MatrixSpArgs &a, hipStream_t s);
 
+// MatrixLookaheadConvolver (matrix_la.hip): one chunk of a dense
+// matrix whose far rows (s >= kMatrixLaQ) are summed once every kMatrixLaQ
+// blocks into a window of kMatrixLaQ future blocks.  `m` is the dense chunk
+// with part = [O][Pn][B] over the near rows (m.P = Pn, m.rpp = near rows per
+// part).  Block numbers are the handle's count of started blocks.
+constexpr int kMatrixLaQ = 8;        // the period Q (fftconv_matrix_lookahead_period)
+constexpr int kMatrixLaMaxLog2B = 9;  // one 16-byte slot per thread: B <= 512
+struct MatrixLaArgs {
+    MatrixArgs m;
+    float2 *far;           // [O][Pf][Q][B] far partial sums, window row = block % Q
+    int Pf;                // far parts (0: no far rows, active <= Q)
+    int rppf;              // far rows per part = ceil(I * (act - Q) / Pf)
+    long long t;           // the block this chunk belongs to
+    long long tv;          // windows anchored before block tv are invalid (tv > t: every output sums in full)
+};
+// the part rule on a row count (matrix_parts_rule's, which takes inputs and active)
+__host__ __device__ inline int matrix_la_parts(long long rows) {
+    const long long p = (rows + 63) / 64;
+    return (int)(p < 1 ? 1 : (p > 64 ? 64 : p));
+}
+// what output o does with its far rows in launch A of block t: 1 = anchor (the
+// windows of blocks t .. t + Q - 1), 2 = full sum of block t alone, 0 = nothing
+// (block t is served by the window of the output's latest anchor).  Output o
+// anchors on blocks t = o (mod Q).
+__host__ __device__ inline int matrix_la_role(long long t, long long tv, int o) {
+    const int ph = (int)(((t - o) % kMatrixLaQ + kMatrixLaQ) % kMatrixLaQ);
+    if (t - ph < tv) return 2;
+    return ph == 0 ? 1 : 0;
+}
+// steady: every output that does not anchor has a window, so launch A holds far
+// workgroups for the anchoring outputs t % Q, t % Q + Q, ... only (else for all)
+__host__ __device__ inline bool matrix_la_steady(long long t, long long tv) { return t - (kMatrixLaQ - 1) >= tv; }
+__host__ __device__ inline int matrix_la_far_outputs(long long t, long long tv, int O) {
+    if (!matrix_la_steady(t, tv)) return O;
+    const int t0 = (int)(t % kMatrixLaQ);
+    return t0 < O ? (O - t0 + kMatrixLaQ - 1) / kMatrixLaQ : 0;
+}
+// the chunk's two launches (32 <= B <= 512)
+hipError_t launch_matrix_la_chunk(int log2b, const MatrixLaArgs &a, hipStream_t s);
+
 // MatrixCrossfadeConvolver (matrix_xf.hip): one chunk of the two
 // matrices A and B of a crossfaded handle while they are in step (equal
 // {current, active, fill} at every call since creation, so X[0] and X[1], ib[0]

@@ -119,6 +119,26 @@ SIGNATURES = {
     "fftconv_matrix_seg_count": (_sz, [_vp]),
     "fftconv_matrix_mac_parts": (_i, [_vp]),
     "fftconv_matrix_state": (_i, [_vp, C.POINTER(_sz)]),
+    "fftconv_matrix_lookahead_init": (_vp, [_i, _sz, _sz, _fp, _sz, _sz, _sz, _sz]),
+    "fftconv_matrix_lookahead_update": (_i, [_vp, _fp, _sz, _sz]),
+    "fftconv_matrix_lookahead_update_device": (_i, [_vp, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_lookahead_reset": (_i, [_vp]),
+    "fftconv_matrix_lookahead_process": (_i, [_vp, _fp, _sz, _fp, _sz]),
+    "fftconv_matrix_lookahead_process_device": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_lookahead_process_device_steps": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _sz, _sz, _vp]),
+    "fftconv_matrix_lookahead_clone": (_vp, [_vp]),
+    "fftconv_matrix_lookahead_destroy": (None, [_vp]),
+    "fftconv_matrix_lookahead_synchronize": (_i, [_vp]),
+    "fftconv_matrix_lookahead_inputs": (_sz, [_vp]),
+    "fftconv_matrix_lookahead_outputs": (_sz, [_vp]),
+    "fftconv_matrix_lookahead_block_size": (_sz, [_vp]),
+    "fftconv_matrix_lookahead_seg_count": (_sz, [_vp]),
+    "fftconv_matrix_lookahead_state": (_i, [_vp, C.POINTER(_sz)]),
+    "fftconv_matrix_lookahead_period": (_i, []),
+    "fftconv_matrix_lookahead_near_parts": (_i, [_vp]),
+    "fftconv_matrix_lookahead_far_parts": (_i, [_vp]),
+    "fftconv_matrix_lookahead_set_windows": (_i, [_vp, _i]),
+    "fftconv_matrix_lookahead_anchors": (_i, [_vp]),
     "fftconv_matrix_sparse_init": (_vp, [_i, _sz, _sz, _sz, _u32p, _u32p, _fp, _sz, _sz, _sz, _sz]),
     "fftconv_matrix_sparse_update": (_i, [_vp, _fp, _sz, _sz]),
     "fftconv_matrix_sparse_update_device": (_i, [_vp, _vp, _sz, _sz, _vp]),
@@ -634,6 +654,94 @@ class MatrixConvolver(_Base):
         return tuple(int(v) for v in out)
 
 
+class MatrixLookaheadConvolver(_Base):
+    """The MatrixConvolver with far-row windows (fftconv.h,
+    "MatrixLookaheadConvolver"): the same inputs x outputs FFTConvolver instances
+    in lockstep, but an output's rows s >= period are summed once every `period`
+    blocks for the next `period` blocks.  Blocks 32..512."""
+
+    _prefix = "matrix_lookahead"
+
+    def __init__(self, h, inputs: int, outputs: int):
+        super().__init__(h, inputs)
+        self.inputs = inputs
+        self.outputs = outputs
+
+    @classmethod
+    def init(cls, responses, max_block_size: int, max_response_length: int, device: int = 0):
+        """responses[O][I][len]: h[o][i] is the response from input i to output o."""
+        r = MatrixConvolver._pairs(responses)
+        O, I, n = r.shape
+        h = lib().fftconv_matrix_lookahead_init(device, I, O, _p(r), n, n, max_block_size, max_response_length)
+        return cls(_handle(h), I, O)
+
+    def update(self, responses):
+        """update() of every pair with responses[O][I][len] (whole matrix only)."""
+        r = MatrixConvolver._pairs(responses, self.inputs, self.outputs)
+        _check(lib().fftconv_matrix_lookahead_update(self._h, _p(r), r.shape[2], r.shape[2]))
+
+    def update_device(self, d_responses: int, response_len: int, stride: int = 0, stream: int = 0):
+        """update() from device memory (pair o * inputs + i at d_responses +
+        4 * pair * stride; stride 0 = one response for every pair), stream-ordered."""
+        _check(self._fn("update_device")(self._h, C.c_void_p(d_responses), response_len, stride,
+                                         C.c_void_p(stream) if stream else None))
+
+    def reset(self):
+        _check(lib().fftconv_matrix_lookahead_reset(self._h))
+
+    def process(self, inp, out_len: int | None = None) -> np.ndarray:
+        """x[inputs][n] -> y[outputs][out_len or n]."""
+        x = _f32(inp)
+        if x.ndim != 2 or x.shape[0] != self.inputs:
+            raise ValueError(f"input must be [{self.inputs}][n]")
+        n_in = x.shape[1]
+        n = n_in if out_len is None else out_len
+        y = np.zeros((self.outputs, n), np.float32)
+        _check(lib().fftconv_matrix_lookahead_process(self._h, _p(x), n_in, _p(y), n))
+        return y
+
+    def clone(self):
+        return MatrixLookaheadConvolver(_handle(lib().fftconv_matrix_lookahead_clone(self._h)), self.inputs,
+                                        self.outputs)
+
+    @property
+    def block_size(self) -> int:
+        return int(lib().fftconv_matrix_lookahead_block_size(self._h))
+
+    @property
+    def seg_count(self) -> int:
+        return int(lib().fftconv_matrix_lookahead_seg_count(self._h))
+
+    @staticmethod
+    def period() -> int:
+        """Q: rows s >= Q are far rows, an output anchors once every Q blocks."""
+        return int(lib().fftconv_matrix_lookahead_period())
+
+    @property
+    def near_parts(self) -> int:
+        """Workgroups sharing one output's near sum, for the current active_seg_count."""
+        return int(lib().fftconv_matrix_lookahead_near_parts(self._h))
+
+    @property
+    def far_parts(self) -> int:
+        """Workgroups sharing one output's far sum (0: no far rows, active <= Q)."""
+        return int(lib().fftconv_matrix_lookahead_far_parts(self._h))
+
+    def set_windows(self, on: bool):
+        """off: every output sums its far rows in full on every block (the same bits)."""
+        _check(lib().fftconv_matrix_lookahead_set_windows(self._h, 1 if on else 0))
+
+    def anchors(self) -> int:
+        """Outputs that anchor when the next block starts."""
+        return int(lib().fftconv_matrix_lookahead_anchors(self._h))
+
+    def state(self):
+        """(current, active_seg_count, input_buffer_fill) of the whole matrix."""
+        out = (C.c_size_t * 3)()
+        _check(lib().fftconv_matrix_lookahead_state(self._h, out))
+        return tuple(int(v) for v in out)
+
+
 class SparseMatrixConvolver(_Base):
     """Matrix convolution over a listed pair set (fftconv.h,
     "SparseMatrixConvolver"): one FFTConvolver instance per listed (output,
@@ -855,7 +963,8 @@ class MatrixTwoStageConvolver(_Base):
 
 __all__ = [
     "Fft", "FFTConvolver", "TwoStageFFTConvolver", "CrossfadeConvolver", "MatrixConvolver",
-    "SparseMatrixConvolver", "MatrixCrossfadeConvolver", "MatrixTwoStageConvolver", "ConvolutionPanic",
+    "MatrixLookaheadConvolver", "SparseMatrixConvolver", "MatrixCrossfadeConvolver", "MatrixTwoStageConvolver",
+    "ConvolutionPanic",
     "NotImplementedInReference", "DeviceError", "complex_size", "compute_tail_block_size", "device_count",
     "lib", "LIB_PATH", "SIGNATURES",
 ]

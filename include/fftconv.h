@@ -63,6 +63,7 @@ typedef struct fftconv_twostage fftconv_twostage;   /* TwoStageFFTConvolver src/
 typedef struct fftconv_crossfade fftconv_crossfade; /* CrossfadeConvolver<FFTConvolver | TwoStageFFTConvolver> src/crossfade_convolver.rs:10-105 */
 typedef struct fftconv_matrix fftconv_matrix;       /* inputs x outputs FFTConvolver instances, summed per output (below) */
 typedef struct fftconv_matrix_sparse fftconv_matrix_sparse; /* one FFTConvolver instance per listed (output, input) pair (below) */
+typedef struct fftconv_matrix_lookahead fftconv_matrix_lookahead; /* the matrix with far-row windows (below) */
 typedef struct fftconv_matrix_crossfade fftconv_matrix_crossfade; /* inputs x outputs CrossfadeConvolver<FFTConvolver> instances (below) */
 typedef struct fftconv_matrix_twostage fftconv_matrix_twostage;   /* inputs x outputs TwoStageFFTConvolver instances (below) */
 
@@ -428,7 +429,7 @@ int fftconv_matrix_state(const fftconv_matrix *h, size_t out3[3]);
  * FFTCONV_E_UNSUPPORTED; init returns NULL on error (fftconv_last_error).
  * Out of scope: a sparse crossfade and a sparse two-stage matrix (those take a
  * dense fftconv_matrix), changing the pattern after init, and any lookahead
- * for matrices. */
+ * for a sparse matrix (the dense one has fftconv_matrix_lookahead). */
 fftconv_matrix_sparse *fftconv_matrix_sparse_init(int device, size_t inputs, size_t outputs, size_t pairs,
                                                   const uint32_t *pair_out, const uint32_t *pair_in,
                                                   const float *responses, size_t response_len,
@@ -468,6 +469,83 @@ size_t fftconv_matrix_sparse_seg_count(const fftconv_matrix_sparse *h);
 int fftconv_matrix_sparse_output_parts(const fftconv_matrix_sparse *h, size_t output);
 /* {current, active_seg_count, input_buffer_fill} as of the calls enqueued so far */
 int fftconv_matrix_sparse_state(const fftconv_matrix_sparse *h, size_t out3[3]);
+
+/* ---- MatrixLookaheadConvolver: far-row windows for the matrix ----
+ * Definition: exactly fftconv_matrix's -- I*O FFTConvolver instances (o, i) in
+ * lockstep, output o the sum over i, one {current, active_seg_count,
+ * input_buffer_fill} -- with the same two departures (non-finite samples are
+ * outside the parity contract; only whole-matrix update).  What differs is the
+ * schedule of the spectral sum, and with it the order of summation.
+ * With the period Q = fftconv_matrix_lookahead_period() (8; part of the
+ * contract) the rows H[o][i][s] (.) X[i][(current + s) % active] of an output
+ * are split at Q.  Near rows 1 <= s < Q are summed on every block.  Far rows
+ * Q <= s < active are summed by an anchor once every Q blocks: output o anchors
+ * on the blocks t = o (mod Q), t = the handle's count of started blocks, and
+ * one walk over its far rows produces the far sums ("window") of blocks t ..
+ * t + Q - 1, so every far H row is read once per Q blocks.  After init, reset,
+ * update and while current >= active (after a shrinking update) an output has
+ * no window until its next anchor, at most Q - 1 blocks later; until then it
+ * sums its far rows in full on every block.
+ * Order of summation (part of the contract): pre[o] = near[o] + far[o], then
+ * the row-0 terms X[i][current] (.) H[o][i][0] in ascending i.
+ *  - near[o]: the rows (i, s), 1 <= s < min(Q, active), flattened i-major, in
+ *    Pn parts (fftconv_matrix_lookahead_near_parts: the rule of
+ *    fftconv_matrix_mac_parts on the near row count); inside a part the row
+ *    groups and their order are the dense matrix's; parts added ascending.
+ *  - far[o]: the rows (i, s), Q <= s < active, flattened i-major, in Pf parts
+ *    (fftconv_matrix_lookahead_far_parts: the same rule on the far row count;
+ *    0 when active <= Q, and then pre[o] = near[o]); inside a part each row
+ *    group takes a contiguous, ascending sub-range of ceil(rows per part /
+ *    groups) rows; groups added ascending, parts added ascending.
+ * Both counts are functions of (inputs, active_seg_count, Q) only.  A block
+ * served from a window and a block that sums everything itself perform the same
+ * operations in the same order, so outputs do not depend on the anchor phase,
+ * on fftconv_matrix_lookahead_set_windows, on `outputs` (a matrix split by
+ * outputs over handles or GPUs computes bit-identical rows), or on how calls
+ * are grouped (process_device_steps equals the separate calls).  They equal
+ * fftconv_matrix's within f32 rounding, not bitwise.
+ * Supported blocks: 32 <= next_power_of_two(max_block_size) <= 512, else
+ * FFTCONV_E_UNSUPPORTED (use fftconv_matrix there); other errors as
+ * fftconv_matrix_init.  Everything is reserved at init: update allocates
+ * nothing and does not wait on the host.
+ * The crossfaded, two-stage and sparse matrices stay without lookahead. */
+fftconv_matrix_lookahead *fftconv_matrix_lookahead_init(int device, size_t inputs, size_t outputs,
+                                                        const float *responses, size_t response_len,
+                                                        size_t response_stride, size_t max_block_size,
+                                                        size_t max_response_length);
+int fftconv_matrix_lookahead_update(fftconv_matrix_lookahead *h, const float *responses, size_t response_len,
+                                    size_t response_stride);
+int fftconv_matrix_lookahead_update_device(fftconv_matrix_lookahead *h, const float *d_responses,
+                                           size_t response_len, size_t response_stride, void *hip_stream);
+int fftconv_matrix_lookahead_reset(fftconv_matrix_lookahead *h); /* :296-306 */
+int fftconv_matrix_lookahead_process(fftconv_matrix_lookahead *h, const float *input, size_t input_len,
+                                     float *output, size_t output_len);
+int fftconv_matrix_lookahead_process_device(fftconv_matrix_lookahead *h, const float *d_input, size_t in_stride,
+                                            float *d_output, size_t out_stride, size_t len, void *hip_stream);
+int fftconv_matrix_lookahead_process_device_steps(fftconv_matrix_lookahead *h, const float *d_input,
+                                                  size_t in_stride, size_t in_step, float *d_output,
+                                                  size_t out_stride, size_t out_step, size_t len, size_t steps,
+                                                  void *hip_stream);
+/* the clone carries the windows and the block count: it continues bit for bit */
+fftconv_matrix_lookahead *fftconv_matrix_lookahead_clone(const fftconv_matrix_lookahead *h);
+void fftconv_matrix_lookahead_destroy(fftconv_matrix_lookahead *h);
+int fftconv_matrix_lookahead_synchronize(fftconv_matrix_lookahead *h);
+size_t fftconv_matrix_lookahead_inputs(const fftconv_matrix_lookahead *h);
+size_t fftconv_matrix_lookahead_outputs(const fftconv_matrix_lookahead *h);
+size_t fftconv_matrix_lookahead_block_size(const fftconv_matrix_lookahead *h);
+size_t fftconv_matrix_lookahead_seg_count(const fftconv_matrix_lookahead *h);
+/* {current, active_seg_count, input_buffer_fill} as of the calls enqueued so far */
+int fftconv_matrix_lookahead_state(const fftconv_matrix_lookahead *h, size_t out3[3]);
+int fftconv_matrix_lookahead_period(void); /* Q */
+int fftconv_matrix_lookahead_near_parts(const fftconv_matrix_lookahead *h);
+int fftconv_matrix_lookahead_far_parts(const fftconv_matrix_lookahead *h);
+/* on = 0: no output anchors, every block sums its far rows in full (the same
+ * bits; for tests and measurements).  on = 1 (default): anchors resume at each
+ * output's next slot. */
+int fftconv_matrix_lookahead_set_windows(fftconv_matrix_lookahead *h, int on);
+/* outputs that anchor when the next block starts (0 while windows are off,
+ * active <= Q or current >= active) */
+int fftconv_matrix_lookahead_anchors(const fftconv_matrix_lookahead *h);
 
 /* ---- MatrixCrossfadeConvolver: crossfaded response switching for the matrix ----
  * A matrix crossfade (inputs I, outputs O) behaves as I*O reference
