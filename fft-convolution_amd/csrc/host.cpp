@@ -26,6 +26,7 @@
 
 #include "../../include/fftconv.h"
 #include "kernels.hpp"
+#include "pair_book.hpp"
 
 using namespace fftconv;
 
@@ -244,7 +245,83 @@ struct PinnedStage {
         }
         return FFTCONV_OK;
     }
+    // upload() with row r going to device row drow[r] (ascending): the rows are
+    // staged once, one H2D copy per run of consecutive device rows
+    int upload_scatter(const float *src, size_t rows, size_t len, size_t stride, float *dst, size_t dpitch,
+                       const uint32_t *drow, hipStream_t s) {
+        if (len == 0 || rows == 0) return FFTCONV_OK;
+        if (!p || n < len) return fail(FFTCONV_E_INVALID, "no host staging for this update");
+        const size_t per = n / len;
+        for (size_t r0 = 0; r0 < rows; r0 += per) {
+            const size_t k = std::min(per, rows - r0);
+            if (int r = acquire()) return r;
+            for (size_t c = 0; c < k; ++c) std::memcpy(p + c * len, src + (r0 + c) * stride, len * sizeof(float));
+            for (size_t c0 = 0; c0 < k;) {
+                size_t c1 = c0 + 1;
+                while (c1 < k && drow[r0 + c1] == drow[r0 + c1 - 1] + 1) ++c1;
+                HIP_TRY(hipMemcpy2DAsync(dst + (size_t)drow[r0 + c0] * dpitch, dpitch * sizeof(float), p + c0 * len,
+                                         len * sizeof(float), len * sizeof(float), c1 - c0, hipMemcpyHostToDevice, s));
+                c0 = c1;
+            }
+            if (int r = release(s)) return r;
+        }
+        return FFTCONV_OK;
+    }
 };
+
+// The device pair lists of update_pairs (matrix_patch.hip) with their pinned
+// host mirror, reserved at creation for O * I pairs each: [0, cap) the pairs to
+// transform, [cap, 2 cap) the pairs to copy.  `busy` guards the mirror's reuse,
+// as PinnedStage's.  `idx` is the host scratch of a call's validated list.
+struct PairLists {
+    DevPtr<uint32_t> d;
+    uint32_t *h = nullptr;
+    size_t cap = 0;
+    hipEvent_t busy = nullptr;
+    bool pending = false;
+    std::vector<uint32_t> idx;
+    PairLists() = default;
+    PairLists(const PairLists &) = delete;
+    PairLists &operator=(const PairLists &) = delete;
+    ~PairLists() {
+        if (busy) {
+            if (pending) (void)hipEventSynchronize(busy);
+            (void)hipEventDestroy(busy);
+        }
+        if (h) (void)hipHostFree(h);
+    }
+    int alloc(size_t pairs) {
+        cap = pairs;
+        if (pairs == 0) return FFTCONV_OK;
+        idx.assign(pairs, 0);
+        if (int r = d.alloc(2 * pairs)) return r;
+        if (hipHostMalloc((void **)&h, 2 * pairs * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) {
+            h = nullptr;
+            return fail(FFTCONV_E_NOMEM, "hipHostMalloc: pair lists");
+        }
+        HIP_TRY(hipEventCreateWithFlags(&busy, hipEventDisableTiming));
+        return FFTCONV_OK;
+    }
+    int acquire() {  // the previous call's lists have left the mirror (normally long done)
+        if (pending) HIP_TRY(hipEventSynchronize(busy));
+        pending = false;
+        return FFTCONV_OK;
+    }
+    uint32_t *tr() { return h; }
+    uint32_t *cp() { return h + cap; }
+    int push(size_t n_tr, size_t n_cp, hipStream_t s) {
+        if (n_tr) HIP_TRY(hipMemcpyAsync(d.p, h, n_tr * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        if (n_cp) HIP_TRY(hipMemcpyAsync(d.p + cap, h + cap, n_cp * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(busy, s));
+        pending = true;
+        return FFTCONV_OK;
+    }
+};
+
+int pair_list_error(PairListError e) {
+    return fail(FFTCONV_E_INVALID, e == PAIRS_RANGE ? "a pair index is out of range"
+                                                    : "the pair list must be strictly ascending in (output, input)");
+}
 
 int lg_tables(int dev, int log2m, LgTab *out);
 
@@ -1864,12 +1941,14 @@ struct MatrixCore {
     size_t S = 0;         // seg_count
     size_t Pmax = 1;      // MAC parts at active = S (the `part` rows per output)
     size_t cur = 0, act = 0, fill = 0;
+    size_t last_len = 0;  // response_len of the last init / update: the length update_pairs pads to
     DevPtr<float2> H, X, pre, part, tw;
     DevPtr<float> ovl, ib, staging;
     hipStream_t stream = nullptr;
     bool own_stream = true;  // false: a MatrixCrossfadeCore's / MatrixTwoStageCore's convolver on its owner's stream
     Scratch scratch;
     PinnedStage hstage;
+    PairLists lists;      // update_pairs (own_stream only: an owner brings its own)
     mutable StreamOrder order;
 
     ~MatrixCore() {
@@ -1913,6 +1992,8 @@ struct MatrixCore {
         if (int r = tw.alloc(2 * B)) return r;
         if (int r = staging.alloc(O * I * ir_len)) return r;       // update() never allocates
         if (int r = hstage.alloc(O * I * ir_len, ir_len)) return r;
+        if (!owner)
+            if (int r = lists.alloc(O * I)) return r;
         std::vector<float2> t(2 * B);
         const size_t N = 2 * B;
         for (size_t k = 0; k < N; ++k) {
@@ -1964,6 +2045,7 @@ struct MatrixCore {
         DeviceGuard g(dev);
         if (int r = alloc_geometry(dev, inputs, outputs, max_block, max_len, owner)) return r;
         if (int r = zero_state(stream)) return r;
+        last_len = len;
         if (S > 0) {
             const bool shared = stride == 0 && O * I > 1;
             if (len)
@@ -1982,6 +2064,7 @@ struct MatrixCore {
         if (pre.n) HIP_TRY(hipMemsetAsync(pre.p, 0, pre.bytes(), s));   // :187
         if (ovl.n) HIP_TRY(hipMemsetAsync(ovl.p, 0, ovl.bytes(), s));   // :188
         act = ceil_div(len, B);                                     // :190 (current untouched)
+        last_len = len;
         return ir_from_device(src, stride, len, len, s);
     }
     int update_host(const float *src, size_t len, size_t stride) {
@@ -1993,6 +2076,72 @@ struct MatrixCore {
         if (len)
             if (int r = hstage.upload(src, shared ? 1 : O * I, len, stride, staging.p, ir_len, stream)) return r;
         return update_device(staging.p, shared ? 0 : ir_len, len, stream);
+    }
+
+    // One patch of H (matrix_patch.hip) from the lists staged in L's mirror:
+    // the first n_tr pairs of L.tr() are transformed from `src` (entry n reads
+    // row n, or -- by_pair -- the row of its pair index), the first n_cp pairs
+    // of L.cp() are copied from Hsrc.  One launch up to kMatrixPatchChunk pairs
+    // per list.
+    int patch_device(PairLists &L, size_t n_tr, size_t n_cp, const float2 *Hsrc, const float *src, size_t stride,
+                     bool by_pair, size_t len_data, size_t len_active, hipStream_t s) {
+        if (int r = L.push(n_tr, n_cp, s)) return r;
+        const size_t step = (size_t)kMatrixPatchChunk;
+        for (size_t c0 = 0; c0 < std::max(n_tr, n_cp); c0 += step) {
+            MatrixPatchArgs a{};
+            a.H = H.p;
+            a.Hsrc = Hsrc;
+            a.src = src;
+            a.src_stride = (long long)stride;
+            a.len_data = (long long)len_data;
+            a.len_active = (long long)len_active;
+            a.tw = tw.p;
+            a.tr = L.d.p + c0;
+            a.cp = L.d.p + L.cap + c0;
+            a.n_tr = (int)(c0 < n_tr ? std::min(step, n_tr - c0) : 0);
+            a.n_cp = (int)(c0 < n_cp ? std::min(step, n_cp - c0) : 0);
+            a.row0 = (int)c0;
+            a.by_pair = by_pair ? 1 : 0;
+            a.S = (int)S;
+            a.pairs = (int)(O * I);
+            a.nt_cp = Variant::current().nt_matrix(H.bytes()) ? 1 : 0;
+            HIP_TRY(launch_matrix_patch(log2b, a, s));
+        }
+        return FFTCONV_OK;
+    }
+
+    // update(R'), R' = the responses this matrix holds with the n listed pairs
+    // (ascending, in L.tr()) replaced by rows 0..n-1 of src, at the length of
+    // the last init / update: update's side effects, and only the
+    // listed pairs are transformed -- every other pair's rows are already the
+    // ones update(R') would write.
+    int update_pairs_device(PairLists &L, size_t n, const float *src, size_t stride, size_t len, hipStream_t s) {
+        if (len > last_len)
+            return fail(FFTCONV_E_INVALID, "update_pairs: response longer than the length the response set was applied at");
+        if (ir_len == 0) return FFTCONV_OK;
+        if (pre.n) HIP_TRY(hipMemsetAsync(pre.p, 0, pre.bytes(), s));
+        if (ovl.n) HIP_TRY(hipMemsetAsync(ovl.p, 0, ovl.bytes(), s));
+        act = ceil_div(last_len, B);
+        return patch_device(L, n, 0, nullptr, src, stride, false, len, last_len, s);
+    }
+    // the C ABI's two variants: d_src == false -- host rows through the pinned staging
+    int update_pairs(size_t n, const uint32_t *pair_out, const uint32_t *pair_in, const float *src, bool d_src,
+                     size_t len, size_t stride, hipStream_t s) {
+        if (n && (!pair_out || !pair_in)) return fail(FFTCONV_E_INVALID, "null pair list");
+        if (n > O * I) return fail(FFTCONV_E_INVALID, "the pair list must be strictly ascending in (output, input)");
+        if (PairListError e = check_pairs(n, pair_out, pair_in, I, O, lists.idx.data())) return pair_list_error(e);
+        if (len > last_len)
+            return fail(FFTCONV_E_INVALID, "update_pairs: response longer than the length the response set was applied at");
+        DeviceGuard g(device);
+        if (int r = order.enter(s)) return r;
+        if (int r = lists.acquire()) return r;
+        std::copy(lists.idx.begin(), lists.idx.begin() + n, lists.tr());
+        if (!d_src && len && n && ir_len) {
+            const bool shared = stride == 0 && n > 1;
+            if (int r = hstage.upload(src, shared ? 1 : n, len, stride, staging.p, ir_len, s)) return r;
+            return update_pairs_device(lists, n, staging.p, shared ? 0 : ir_len, len, s);
+        }
+        return update_pairs_device(lists, n, src, stride, len, s);
     }
 
     int process_device(const float *din, size_t is, float *dout, size_t os, size_t n, hipStream_t s) {
@@ -2059,12 +2208,13 @@ struct MatrixCore {
         if (int r = o.order.drain(o.stream)) return r;
         device = o.device;
         I = o.I; O = o.O; ir_len = o.ir_len; B = o.B; log2b = o.log2b; S = o.S; Pmax = o.Pmax;
-        cur = o.cur; act = o.act; fill = o.fill;
+        cur = o.cur; act = o.act; fill = o.fill; last_len = o.last_len;
         if (owner) {
             stream = owner;
             own_stream = false;
         } else {
             HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+            if (int r = lists.alloc(O * I)) return r;
         }
         auto cp = [&](auto &dst, const auto &src) -> int {
             if (int r = dst.alloc(src.n)) return r;
@@ -2548,6 +2698,10 @@ struct MatrixCrossfadeCore {
     Scratch scratch;
     mutable StreamOrder order;
     PinnedStage hstage;
+    // update_pairs: the diff set D of A and B and the pending
+    // partial update's list (host side, pair_book.hpp), the device lists
+    PairBook book;
+    PairLists lists;
 
     int check_poisoned() const {
         return poisoned ? fail(FFTCONV_E_DEVICE, "matrix crossfade handle unusable: an earlier process() failed "
@@ -2573,6 +2727,8 @@ struct MatrixCrossfadeCore {
         if (int r = hstage.alloc(hstage_count, stage_row)) return r;
         if (int r = buf_a.alloc(O * max_buffer_size)) return r;
         if (int r = buf_b.alloc(O * max_buffer_size)) return r;
+        if (int r = lists.alloc(O * I)) return r;
+        book.init(O * I);
         return mix_tab.alloc(max_buffer_size + 1);
     }
 
@@ -2610,6 +2766,123 @@ struct MatrixCrossfadeCore {
         const int to = xf.target == 0 ? 1 : 0;
         if (int r = (to ? *b : *a).update_device(src, stride, len, s)) return r;
         xf.fade_into(to);
+        book.whole_applied();  // every pair of A and B may differ now
+        return FFTCONV_OK;
+    }
+
+    // The partial swap: update(R') of the convolver T that is not
+    // the target, R' = the target's responses with the n listed pairs (`lst`,
+    // ascending) replaced at len_active samples, then the fade into T.  T's
+    // spectra differ from the target's in the pairs of D only, so the pairs of
+    // D minus lst are copied from the target's spectra, the listed ones are
+    // transformed from `src` (entry k reads row k, or -- by_pair -- row lst[k]),
+    // and D = lst.  One launch; no allocation, no host wait beyond the lists'
+    // mirror.
+    int swap_pairs_device(const uint32_t *lst, size_t n, const float *src, size_t stride, bool by_pair,
+                          size_t len_data, size_t len_active, hipStream_t s) {
+        const int to = xf.target == 0 ? 1 : 0;
+        MatrixCore &t = to ? *b : *a, &other = to ? *a : *b;
+        if (len_active > t.ir_len) return fail(FFTCONV_E_INVALID, "New impulse response is longer than initialized length");
+        if (int r = lists.acquire()) return r;
+        if (n) std::copy(lst, lst + n, lists.tr());
+        const size_t n_cp = book.partial_applied(lst, n, lists.cp());
+        if (t.ir_len != 0) {
+            if (t.pre.n) HIP_TRY(hipMemsetAsync(t.pre.p, 0, t.pre.bytes(), s));   // update's side effects (:186-190)
+            if (t.ovl.n) HIP_TRY(hipMemsetAsync(t.ovl.p, 0, t.ovl.bytes(), s));
+            t.act = ceil_div(len_active, t.B);
+            t.last_len = len_active;
+            if (int r = t.patch_device(lists, n, n_cp, other.H.p, src, stride, by_pair, len_data, len_active, s)) return r;
+        }
+        xf.fade_into(to);
+        return FFTCONV_OK;
+    }
+
+    // the pending response, whole or partial, into the convolver that is not the target
+    int apply_pending(hipStream_t s) {
+        if (!book.partial) return swap_device(stored.p, stored_stride, stored_len, s);
+        const size_t n = book.pending_list(lists.idx.data());
+        if (int r = swap_pairs_device(lists.idx.data(), n, stored.p, stored_len, true, stored_len, stored_len, s)) return r;
+        book.clear_pending();
+        return FFTCONV_OK;
+    }
+
+    // rows k of a listed update (`len` samples each, on the host or the device)
+    // to the stored response's rows lst[k], zero-padded to stored_len
+    int store_rows(const uint32_t *lst, size_t n, const float *src, bool d_src, size_t len, size_t stride, hipStream_t s) {
+        for (size_t k0 = 0; k0 < n;) {
+            size_t k1 = k0 + 1;
+            while (k1 < n && lst[k1] == lst[k1 - 1] + 1) ++k1;
+            float *dst = stored.p + (size_t)lst[k0] * stored_len;
+            if (len < stored_len) HIP_TRY(hipMemsetAsync(dst, 0, (k1 - k0) * stored_len * sizeof(float), s));
+            if (len && d_src) {
+                if (stride >= len) {
+                    HIP_TRY(hipMemcpy2DAsync(dst, stored_len * sizeof(float), src + k0 * stride, stride * sizeof(float),
+                                             len * sizeof(float), k1 - k0, hipMemcpyDeviceToDevice, s));
+                } else {  // (stride 0: one response for every listed pair)
+                    for (size_t k = k0; k < k1; ++k)
+                        HIP_TRY(hipMemcpyAsync(dst + (k - k0) * stored_len, src + k * stride, len * sizeof(float),
+                                               hipMemcpyDeviceToDevice, s));
+                }
+            }
+            k0 = k1;
+        }
+        if (len && !d_src) return hstage.upload_scatter(src, n, len, stride, stored.p, stored_len, lst, s);
+        return FFTCONV_OK;
+    }
+
+    // update_pairs: update(R'), R' = the base set with the listed pairs replaced
+    // (DESIGN §4o).  `s` is ordered behind the handle's previous work.
+    int update_pairs(size_t n, const uint32_t *pair_out, const uint32_t *pair_in, const float *src, bool d_src,
+                     size_t len, size_t stride, hipStream_t s) {
+        if (int r = check_poisoned()) return r;
+        if (n && (!pair_out || !pair_in)) return fail(FFTCONV_E_INVALID, "null pair list");
+        if (n > O * I) return fail(FFTCONV_E_INVALID, "the pair list must be strictly ascending in (output, input)");
+        uint32_t *lst = lists.idx.data();
+        if (PairListError e = check_pairs(n, pair_out, pair_in, I, O, lst)) return pair_list_error(e);
+        MatrixCore &t = xf.target == 0 ? *b : *a, &base = xf.target == 0 ? *a : *b;
+        const bool fading = is_crossfading();
+        DeviceGuard g(device);
+        if (!fading && !response_pending) {
+            // the base set is the target convolver's, at the length it was applied at
+            const size_t lenp = base.last_len;
+            if (len > lenp)
+                return fail(FFTCONV_E_INVALID, "update_pairs: response longer than the length the response set was applied at");
+            if (int r = order.enter(s)) return r;
+            if (!d_src && len && n && t.ir_len) {
+                const bool shared = stride == 0 && n > 1;
+                if (int r = hstage.upload(src, shared ? 1 : n, len, stride, t.staging.p, t.ir_len, s)) return r;
+                return swap_pairs_device(lst, n, t.staging.p, shared ? 0 : t.ir_len, false, len, lenp, s);
+            }
+            return swap_pairs_device(lst, n, src, stride, false, len, lenp, s);
+        }
+        // the base set is, or becomes, a stored response of stored_len samples
+        if (len > stored_len)
+            return fail(FFTCONV_E_INVALID, fading ? "assertion failed: response_len <= self.stored_response.len()"
+                                                  : "update_pairs: response longer than the stored response");
+        const bool whole = response_pending && !book.partial;
+        if (!whole && ceil_div(stored_len, base.B) != base.act)
+            return fail(FFTCONV_E_UNSUPPORTED, "update_pairs during a fade: the stored length gives another active segment "
+                                               "count than the base convolver's, so zero-padding cannot reproduce update()");
+        if (!fading && stored_len > t.ir_len)
+            return fail(FFTCONV_E_INVALID, "New impulse response is longer than initialized length");
+        if (int r = order.enter(s)) return r;
+        if (whole && stored_stride == 0 && O * I > 1) {
+            // a shared stored response: every pair gets its own row first
+            for (size_t k = 1; k < O * I; k *= 2)
+                HIP_TRY(hipMemcpyAsync(stored.p + k * stored_len, stored.p, std::min(k, O * I - k) * stored_len * sizeof(float),
+                                       hipMemcpyDeviceToDevice, s));
+            stored_stride = stored_len;
+        }
+        if (int r = store_rows(lst, n, src, d_src, len, stride, s)) return r;
+        if (!whole) {
+            book.merge_pending(lst, n);  // (a pair listed twice: the later rows have replaced the earlier ones)
+            stored_stride = stored_len;
+        }
+        response_pending = true;
+        if (!fading) {  // the fade has ended: update(R') swaps at once
+            if (int r = apply_pending(s)) return r;
+            response_pending = false;
+        }
         return FFTCONV_OK;
     }
 
@@ -2629,6 +2902,7 @@ struct MatrixCrossfadeCore {
                 if (int r = hstage.upload(src, rows, len, stride, t.staging.p, t.ir_len, stream)) return r;
             if (int r = swap_device(t.staging.p, shared ? 0 : t.ir_len, len, stream)) return r;
             response_pending = false;
+            book.clear_pending();
             return FFTCONV_OK;
         }
         if (len > stored_len) return fail(FFTCONV_E_INVALID, "assertion failed: response_len <= self.stored_response.len()");
@@ -2639,6 +2913,7 @@ struct MatrixCrossfadeCore {
             if (int r = hstage.upload(src, rows, len, stride, stored.p, stored_len, stream)) return r;
         stored_stride = shared ? 0 : stored_len;
         response_pending = true;
+        book.clear_pending();  // (a whole response replaces a pending partial one)
         return FFTCONV_OK;
     }
 
@@ -2649,6 +2924,7 @@ struct MatrixCrossfadeCore {
         if (!is_crossfading()) {
             if (int r = swap_device(src, stride, len, s)) return r;
             response_pending = false;
+            book.clear_pending();
             return FFTCONV_OK;
         }
         if (len > stored_len) return fail(FFTCONV_E_INVALID, "assertion failed: response_len <= self.stored_response.len()");
@@ -2659,6 +2935,7 @@ struct MatrixCrossfadeCore {
                                      len * sizeof(float), shared ? 1 : O * I, hipMemcpyDeviceToDevice, s));
         stored_stride = shared ? 0 : stored_len;
         response_pending = true;
+        book.clear_pending();  // (a whole response replaces a pending partial one)
         return FFTCONV_OK;
     }
 
@@ -2695,7 +2972,7 @@ struct MatrixCrossfadeCore {
         if (int r = check_poisoned()) return r;
         if (out_len > max_buffer_size) return fail(FFTCONV_E_INVALID, "output longer than max_buffer_size (index out of bounds)");
         if (!is_crossfading() && response_pending) {                    // :67-70
-            if (int r = swap_device(stored.p, stored_stride, stored_len, s)) return r;
+            if (int r = apply_pending(s)) return r;
             response_pending = false;
         }
         const size_t m = max_buffer_size;
@@ -2794,6 +3071,7 @@ struct MatrixCrossfadeCore {
         if (int r = a->clone_from(*o.a, stream)) return r;
         if (int r = b->clone_from(*o.b, stream)) return r;
         if (int r = alloc_buffers(o.hstage.n)) return r;
+        book.copy_from(o.book);
         if (stored.n) HIP_TRY(hipMemcpyAsync(stored.p, o.stored.p, stored.bytes(), hipMemcpyDeviceToDevice, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         return FFTCONV_OK;
@@ -3741,6 +4019,19 @@ int fftconv_matrix_update_device(fftconv_matrix *h, const float *d_responses, si
     if (int r = h->core.order.enter(s)) return r;
     return h->core.update_device(d_responses, response_stride, response_len, s);
 }
+int fftconv_matrix_update_pairs(fftconv_matrix *h, size_t n_pairs, const uint32_t *pair_out, const uint32_t *pair_in,
+                                const float *responses, size_t response_len, size_t response_stride) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.update_pairs(n_pairs, pair_out, pair_in, responses, false, response_len, response_stride,
+                                h->core.stream);
+}
+int fftconv_matrix_update_pairs_device(fftconv_matrix *h, size_t n_pairs, const uint32_t *pair_out,
+                                       const uint32_t *pair_in, const float *d_responses, size_t response_len,
+                                       size_t response_stride, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.update_pairs(n_pairs, pair_out, pair_in, d_responses, true, response_len, response_stride,
+                                (hipStream_t)hip_stream);
+}
 int fftconv_matrix_reset(fftconv_matrix *h) {
     if (!h) return fail(FFTCONV_E_INVALID, "null handle");
     DeviceGuard g(h->core.device);
@@ -3994,6 +4285,27 @@ int fftconv_matrix_crossfade_update_device(fftconv_matrix_crossfade *h, const fl
     hipStream_t s = (hipStream_t)hip_stream;
     if (int r = h->core.order.enter(s)) return r;
     return h->core.update_device(d_responses, response_len, response_stride, s);
+}
+int fftconv_matrix_crossfade_update_pairs(fftconv_matrix_crossfade *h, size_t n_pairs, const uint32_t *pair_out,
+                                          const uint32_t *pair_in, const float *responses, size_t response_len,
+                                          size_t response_stride) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.update_pairs(n_pairs, pair_out, pair_in, responses, false, response_len, response_stride,
+                                h->core.stream);
+}
+int fftconv_matrix_crossfade_update_pairs_device(fftconv_matrix_crossfade *h, size_t n_pairs, const uint32_t *pair_out,
+                                                 const uint32_t *pair_in, const float *d_responses,
+                                                 size_t response_len, size_t response_stride, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.update_pairs(n_pairs, pair_out, pair_in, d_responses, true, response_len, response_stride,
+                                (hipStream_t)hip_stream);
+}
+size_t fftconv_matrix_crossfade_diff_pairs(const fftconv_matrix_crossfade *h) { return h ? h->core.book.nd : 0; }
+int fftconv_matrix_crossfade_last_patch(const fftconv_matrix_crossfade *h, size_t out2[2]) {
+    if (!h || !out2) return fail(FFTCONV_E_INVALID, "null handle");
+    out2[0] = h->core.book.last[0];
+    out2[1] = h->core.book.last[1];
+    return FFTCONV_OK;
 }
 int fftconv_matrix_crossfade_reset(fftconv_matrix_crossfade *h) {
     if (!h) return fail(FFTCONV_E_INVALID, "null handle");

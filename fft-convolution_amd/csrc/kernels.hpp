@@ -503,6 +503,32 @@ struct MatrixXfArgs {
 // the chunk's two launches (32 <= B <= 8192)
 hipError_t launch_matrix_xf_chunk(int log2b, const MatrixXfArgs &a, hipStream_t s);
 
+// update_pairs (matrix_patch.hip): patch the spectra H of one matrix
+// for listed pairs (pair = o * I + i) in one launch -- the pairs of `tr` are
+// transformed from their response rows (the bits launch_ir_segments writes),
+// the pairs of `cp` are copied, all S rows, from another matrix's spectra.  A
+// pair is in at most one list.
+constexpr int kMatrixPatchChunk = 32768;  // pairs per list and launch (as MatrixCore::ir_from_device)
+struct MatrixPatchArgs {
+    float2 *H;             // [O*I][S][B] the patched spectra
+    const float2 *Hsrc;    // [O*I][S][B] the copy's source (unused when n_cp == 0)
+    const float *src;      // response rows of the transform
+    long long src_stride;  // floats between rows
+    long long len_data;    // samples present in a row
+    long long len_active;  // rows at or past ceil(len_active / B) are zeroed
+    const float2 *tw;      // W_N^k, k < N = 2B
+    const uint32_t *tr;    // [n_tr] pairs to transform
+    const uint32_t *cp;    // [n_cp] pairs to copy
+    int n_tr, n_cp;
+    int row0;              // by_pair == 0: list entry n reads row row0 + n
+    int by_pair;           // 1: list entry n reads row tr[n] (rows kept at the pairs' own positions)
+    int S;
+    int pairs;             // O * I
+    int nt_cp;             // nontemporal loads of the copy (Variant::nt_matrix of one H)
+    int gx, cpb;           // set by the launcher: transform / copy workgroups per pair
+};
+hipError_t launch_matrix_patch(int log2b, const MatrixPatchArgs &a, hipStream_t s);
+
 // MatrixTwoStageConvolver (matrix_ts.hip): one aligned call -- a
 // whole head block on a block boundary of the tail period -- of the head [0]
 // and tail0 [1] matrices, which then have equal {current, active} and input

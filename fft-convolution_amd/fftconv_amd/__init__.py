@@ -106,6 +106,8 @@ SIGNATURES = {
     "fftconv_matrix_init": (_vp, [_i, _sz, _sz, _fp, _sz, _sz, _sz, _sz]),
     "fftconv_matrix_update": (_i, [_vp, _fp, _sz, _sz]),
     "fftconv_matrix_update_device": (_i, [_vp, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_update_pairs": (_i, [_vp, _sz, _u32p, _u32p, _fp, _sz, _sz]),
+    "fftconv_matrix_update_pairs_device": (_i, [_vp, _sz, _u32p, _u32p, _vp, _sz, _sz, _vp]),
     "fftconv_matrix_reset": (_i, [_vp]),
     "fftconv_matrix_process": (_i, [_vp, _fp, _sz, _fp, _sz]),
     "fftconv_matrix_process_device": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _vp]),
@@ -160,6 +162,10 @@ SIGNATURES = {
     "fftconv_matrix_crossfade_new": (_vp, [_vp, _sz, _sz, _sz]),
     "fftconv_matrix_crossfade_update": (_i, [_vp, _fp, _sz, _sz]),
     "fftconv_matrix_crossfade_update_device": (_i, [_vp, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_crossfade_update_pairs": (_i, [_vp, _sz, _u32p, _u32p, _fp, _sz, _sz]),
+    "fftconv_matrix_crossfade_update_pairs_device": (_i, [_vp, _sz, _u32p, _u32p, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_crossfade_diff_pairs": (_sz, [_vp]),
+    "fftconv_matrix_crossfade_last_patch": (_i, [_vp, C.POINTER(_sz)]),
     "fftconv_matrix_crossfade_reset": (_i, [_vp]),
     "fftconv_matrix_crossfade_process": (_i, [_vp, _fp, _sz, _fp, _sz]),
     "fftconv_matrix_crossfade_process_device": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _vp]),
@@ -579,7 +585,41 @@ class CrossfadeConvolver(_Base):
                                   self.max_buffer_size, self.inner)
 
 
-class MatrixConvolver(_Base):
+def _pair_arrays(pairs):
+    """(output, input) tuples -> the two uint32 arrays of the C ABI."""
+    pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
+    if pr.size and (pr.min() < 0 or pr.max() >= 1 << 32):
+        raise ValueError("pair indices must fit 32 unsigned bits")
+    return np.ascontiguousarray(pr[:, 0].astype(np.uint32)), np.ascontiguousarray(pr[:, 1].astype(np.uint32))
+
+
+class _UpdatePairs:
+    """update_pairs of the dense and the crossfaded matrix (fftconv.h): update(R'),
+    R' = the responses the handle holds with the listed pairs replaced."""
+
+    def update_pairs(self, pairs, responses):
+        """pairs: (output, input) tuples, strictly ascending; responses[n][len]
+        is the new response of pairs[n], zero-padded to the held set's length."""
+        po, pi = _pair_arrays(pairs)
+        r = _f32(responses)
+        if r.ndim != 2 or r.shape[0] != len(po):
+            if len(po) == 0 and r.size == 0:
+                r = np.zeros((0, 0), np.float32)
+            else:
+                raise ValueError("responses must be [pairs][len]")
+        _check(self._fn("update_pairs")(self._h, len(po), po.ctypes.data_as(_u32p), pi.ctypes.data_as(_u32p), _p(r),
+                                        r.shape[1], r.shape[1]))
+
+    def update_pairs_device(self, pairs, d_responses: int, response_len: int, stride: int = 0, stream: int = 0):
+        """update_pairs() from device memory (row n at d_responses + 4 * n *
+        stride belongs to pairs[n]; the pair list is host data), stream-ordered."""
+        po, pi = _pair_arrays(pairs)
+        _check(self._fn("update_pairs_device")(self._h, len(po), po.ctypes.data_as(_u32p), pi.ctypes.data_as(_u32p),
+                                               C.c_void_p(d_responses), response_len, stride,
+                                               C.c_void_p(stream) if stream else None))
+
+
+class MatrixConvolver(_UpdatePairs, _Base):
     """Multi-input multi-output partitioned convolution (fftconv.h,
     "MatrixConvolver"): y[o] = sum_i x[i] * h[o][i], as inputs x outputs
     FFTConvolver instances in lockstep with one delay line per input."""
@@ -607,7 +647,7 @@ class MatrixConvolver(_Base):
         return cls(_handle(h), I, O)
 
     def update(self, responses):
-        """update() of every pair with responses[O][I][len] (whole matrix only)."""
+        """update() of every pair with responses[O][I][len]."""
         r = self._pairs(responses, self.inputs, self.outputs)
         _check(lib().fftconv_matrix_update(self._h, _p(r), r.shape[2], r.shape[2]))
 
@@ -830,7 +870,7 @@ class SparseMatrixConvolver(_Base):
         return tuple(int(v) for v in out)
 
 
-class MatrixCrossfadeConvolver(_Base):
+class MatrixCrossfadeConvolver(_UpdatePairs, _Base):
     """Crossfaded response switching for the matrix (fftconv.h,
     "MatrixCrossfadeConvolver"): inputs x outputs CrossfadeConvolver<FFTConvolver>
     instances in lockstep, one crossfader, the mix applied to the per-output sums."""
@@ -871,6 +911,24 @@ class MatrixCrossfadeConvolver(_Base):
         4 * pair * stride; stride 0 = one response for every pair), stream-ordered."""
         _check(self._fn("update_device")(self._h, C.c_void_p(d_responses), response_len, stride,
                                          C.c_void_p(stream) if stream else None))
+
+    def update_input(self, i: int, responses):
+        """update_pairs of every pair that reads input i: responses[O][len]."""
+        self.update_pairs([(o, i) for o in range(self.outputs)], responses)
+
+    def update_output(self, o: int, responses):
+        """update_pairs of every pair that feeds output o: responses[I][len]."""
+        self.update_pairs([(o, i) for i in range(self.inputs)], responses)
+
+    def diff_pairs(self) -> int:
+        """|D|: the pairs whose spectra may differ between the two convolvers."""
+        return int(lib().fftconv_matrix_crossfade_diff_pairs(self._h))
+
+    def last_patch(self):
+        """(pairs transformed, pairs copied) by the last applied swap."""
+        out = (C.c_size_t * 2)()
+        _check(lib().fftconv_matrix_crossfade_last_patch(self._h, out))
+        return tuple(int(v) for v in out)
 
     def reset(self):
         _check(lib().fftconv_matrix_crossfade_reset(self._h))

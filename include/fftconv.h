@@ -346,9 +346,15 @@ int fftconv_crossfade_synchronize(fftconv_crossfade *h);
  *    reproduced with a shared delay line: output values are unspecified while
  *    a non-finite sample is inside the delay line or the overlap, the state
  *    advances normally, and outputs are exact again once the sample has left.
- *  - Only whole-matrix update: update() zeroes overlap and pre_multiplied per
- *    instance (:186-188), which the matrix keeps summed per output, so a
- *    per-pair update cannot match the definition and is not offered.
+ *  - Updates are updates of the whole matrix: update() zeroes overlap and
+ *    pre_multiplied per instance (:186-188), which the matrix keeps summed per
+ *    output, so updating one instance alone cannot match the definition.
+ *    fftconv_matrix_update_pairs (and the crossfaded matrix's, below) is
+ *    therefore DEFINED as update(R'), R' = the response set the matrix holds
+ *    with the listed pairs replaced: every output's overlap and pre_multiplied
+ *    are zeroed as update does, and only the listed pairs are uploaded and
+ *    transformed.  The sparse, lookahead and two-stage matrices offer the
+ *    whole update only.
  * Responses: pair p = o * inputs + i at responses + p * response_stride
  * (response_stride 0 = one response for every pair).  Supported blocks:
  * 32 <= next_power_of_two(max_block_size) <= 8192, else FFTCONV_E_UNSUPPORTED;
@@ -362,6 +368,22 @@ int fftconv_matrix_update(fftconv_matrix *h, const float *responses, size_t resp
                           size_t response_stride);
 int fftconv_matrix_update_device(fftconv_matrix *h, const float *d_responses, size_t response_len,
                                  size_t response_stride, void *hip_stream);
+/* update(R'), bit for bit in outputs and state: R' = the responses of the last
+ * init / update with the n_pairs listed pairs replaced, at THAT call's
+ * response_len (row n of `responses`, response_len samples, belongs to pair
+ * (pair_out[n], pair_in[n]) and is zero-padded to it; a longer response_len is
+ * FFTCONV_E_INVALID).  The pair list is strictly ascending in o * inputs + i,
+ * as fftconv_matrix_sparse_init's: an unsorted, repeated or out-of-range pair is
+ * FFTCONV_E_INVALID and the handle is unchanged; an empty list is update(R).
+ * response_stride 0 = one response for every listed pair.  pair_out / pair_in
+ * are host arrays in both variants.  No allocation; the host waits no more
+ * than in fftconv_matrix_update. */
+int fftconv_matrix_update_pairs(fftconv_matrix *h, size_t n_pairs, const uint32_t *pair_out,
+                                const uint32_t *pair_in, const float *responses, size_t response_len,
+                                size_t response_stride);
+int fftconv_matrix_update_pairs_device(fftconv_matrix *h, size_t n_pairs, const uint32_t *pair_out,
+                                       const uint32_t *pair_in, const float *d_responses, size_t response_len,
+                                       size_t response_stride, void *hip_stream);
 int fftconv_matrix_reset(fftconv_matrix *h); /* :296-306 */
 /* input [inputs][input_len], output [outputs][output_len], host memory;
  * input_len < output_len is FFTCONV_E_INVALID. */
@@ -571,7 +593,9 @@ int fftconv_matrix_lookahead_anchors(const fftconv_matrix_lookahead *h);
  *    max_buffer_size is FFTCONV_E_INVALID.
  *  - reset is todo!() (:80-82): FFTCONV_E_UNIMPLEMENTED.
  * The matrix's departures carry over: non-finite samples are outside the
- * contract, only whole-matrix updates.  Pairs and strides as fftconv_matrix_*.
+ * contract, and an update is an update of the whole matrix -- update_pairs
+ * (below) is update(R') with the work of the listed pairs.  Pairs and strides as
+ * fftconv_matrix_*.
  * Paths (fftconv_matrix_crossfade_path), chosen by the handle's state only --
  * every path computes the same bits:
  *   0  composition: A and B as two plain matrices, then the mix kernel.  Taken
@@ -600,6 +624,48 @@ int fftconv_matrix_crossfade_update(fftconv_matrix_crossfade *h, const float *re
                                     size_t response_stride);
 int fftconv_matrix_crossfade_update_device(fftconv_matrix_crossfade *h, const float *d_responses,
                                            size_t response_len, size_t response_stride, void *hip_stream);
+/* update_pairs(pairs, responses, len) is update(R'), bit for bit in outputs and
+ * in state (is_crossfading, path, what a later call does); R' = the base set
+ * with the listed pairs replaced, at the base set's length len':
+ *  - base set: the pending stored response if one is pending (len' = the
+ *    stored length, max_response_length of new()), else the responses of the
+ *    convolver the crossfader targets -- the one heard or faded into (len' =
+ *    the response_len of that convolver's last init / update);
+ *  - row n of `responses` (response_len samples) belongs to pair (pair_out[n],
+ *    pair_in[n]) and is zero-padded to len'; response_len > len' is
+ *    FFTCONV_E_INVALID; while a fade is under way response_len beyond the
+ *    stored length is the reference's assert, as for update;
+ *  - the pair list is strictly ascending in o * inputs + i: an unsorted,
+ *    repeated or out-of-range pair is FFTCONV_E_INVALID, the handle unchanged;
+ *    an empty list is update(base set);
+ *  - so: no fade under way -> the swap happens at once; else the rows are
+ *    stored and applied by the first process() after the fade; a second
+ *    update_pairs during the fade merges into the first (the later call wins a
+ *    pair listed twice); a later whole update replaces a pending partial one.
+ * The work is proportional to what changed.  The handle keeps the set D of
+ * pairs whose spectra may differ between its two convolvers (empty after new /
+ * init, every pair after a whole update).  A partial swap copies the spectra of
+ * D minus the listed pairs from the target convolver, transforms the listed
+ * pairs, and leaves D = the listed pairs: one launch.  Where no spectra exist to
+ * copy from -- a whole response is pending -- the stored rows are patched and
+ * the whole swap runs (D = every pair).  The one unsupported case: a partial
+ * update during a fade when ceil(stored length / block) differs from the
+ * target convolver's active_seg_count (zero-padding cannot reproduce update
+ * then): FFTCONV_E_UNSUPPORTED, handle unchanged.
+ * pair_out / pair_in are host arrays in both variants; response_stride 0 = one
+ * response for every listed pair.  No allocation, no host wait beyond update's. */
+int fftconv_matrix_crossfade_update_pairs(fftconv_matrix_crossfade *h, size_t n_pairs, const uint32_t *pair_out,
+                                          const uint32_t *pair_in, const float *responses, size_t response_len,
+                                          size_t response_stride);
+int fftconv_matrix_crossfade_update_pairs_device(fftconv_matrix_crossfade *h, size_t n_pairs,
+                                                 const uint32_t *pair_out, const uint32_t *pair_in,
+                                                 const float *d_responses, size_t response_len,
+                                                 size_t response_stride, void *hip_stream);
+/* |D|: the pairs whose spectra may differ between the two convolvers */
+size_t fftconv_matrix_crossfade_diff_pairs(const fftconv_matrix_crossfade *h);
+/* the last applied swap: out2 = {pairs transformed, pairs copied}; a whole
+ * update gives {inputs * outputs, 0} */
+int fftconv_matrix_crossfade_last_patch(const fftconv_matrix_crossfade *h, size_t out2[2]);
 int fftconv_matrix_crossfade_reset(fftconv_matrix_crossfade *h);
 /* input [inputs][input_len], output [outputs][output_len], host memory. */
 int fftconv_matrix_crossfade_process(fftconv_matrix_crossfade *h, const float *input, size_t input_len,
