@@ -11,8 +11,9 @@
 //   1. spectra  R2C of every block (wave_r2c_post, as la_step's chain) into a
 //               staging row per step -- not the ring: block t0+j overwrites
 //               block t0+j-act, which the steps before it still sum;
-//   2. walk     per (channel, 64-slot bin slice, 8-step window slice) every
-//               chain of the canonical order with 8 accumulators (la_walk_x):
+//   2. walk     per (channel, 64-slot bin slice, window slice of JW = 16 or
+//               8 steps) every chain of the canonical order with JW
+//               accumulators (la_walk_x):
 //               levels 3 and 2 in their NG groups (one wave each), then the
 //               level-1 and the near chain on two waves, combined in LDS in
 //               the full pass's order (la_step, anyfull) into one `pre` row
@@ -47,13 +48,22 @@
 namespace fftconv {
 
 static_assert(2 * LA_BATCH_MAX <= 2 * LA_PT, "staging and pre rows fit the channel's windows");
-static_assert(LA_BATCH_MAX % LA_JW == 0, "whole window slices");
-
-// rows in flight per lane of the batch walk (H and X each; 3 spills 11 and
-// 4 spills 45 registers at the 128 a workgroup of four per CU may use)
-#ifndef FFTCONV_LAB_U
-#define FFTCONV_LAB_U LA_UF
-#endif
+// The walk's window slice and rows in flight per lane (H and X each).  The
+// walk runs at the rate of its L2 misses; 16-step slices issue
+// half the row requests of 8-step ones and miss less.  16 accumulators and
+// the 19-row X ring take the 256 registers of two workgroups per CU (4 rows
+// in flight spill 3).  A slice costs the same whatever part of it is live and
+// the grid is half the 8-step one, so short grids and calls whose last 16-step
+// slice is at most half full keep the 8-step slices (4 workgroups per CU, 2
+// rows in flight: 3 spill 11 of the 128 registers): lab_wide.
+constexpr int LAB_JW = 16, LAB_U = 3;
+constexpr int LAB_WIDE_MIN_WG = 512;  // 16-step slices from two workgroups per CU up (profiles/batch_walk/ab_calls.txt)
+static_assert(LA_BATCH_MAX % LAB_JW == 0 && LAB_JW % LA_NG == 0 && LA_JW % LA_NG == 0,
+              "whole window slices, split evenly over the waves");
+__host__ __device__ constexpr bool lab_wide(int channels, int nsl, int k) {
+    return (k - 1) % LAB_JW >= LAB_JW / 2 &&
+           (channels + 7) / 8 * 8 * nsl * ((k + LAB_JW - 1) / LAB_JW) >= LAB_WIDE_MIN_WG;
+}
 
 // staging row j (the spectrum of chunk step j) / pre row j of channel c
 template <int LOG2B>
@@ -145,19 +155,18 @@ struct LabX {
     }
 };
 
-template <int LOG2B>
+template <int LOG2B, int JW>
 struct LabWalk {
-    // the groups' sums [NG][JW][FS] | W2 + W3 of the slice's steps [JW][FS] (float4): 40 KB, four per CU
-    static constexpr size_t red_bytes = (size_t)LA_NG * LA_JW * LaGeo<LOG2B>::FS * 16;
-    static constexpr size_t bytes = red_bytes + (size_t)LA_JW * LaGeo<LOG2B>::FS * 16;
+    // the groups' sums [NG][JW][FS] | W2 + W3 of the slice's steps [JW][FS] (float4): 5 KB per step
+    static constexpr size_t red_bytes = (size_t)LA_NG * JW * LaGeo<LOG2B>::FS * 16;
+    static constexpr size_t bytes = red_bytes + (size_t)JW * LaGeo<LOG2B>::FS * 16;
 };
-template <int LOG2B, int U>
-__global__ __launch_bounds__(LA_NT, 4) void la_batch_walk_kernel(ProcArgs a, LaBatchArgs bt) {
+template <int LOG2B, int JW, int U, int WPC>
+__global__ __launch_bounds__(LA_NT, WPC) void la_batch_walk_kernel(ProcArgs a, LaBatchArgs bt) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     using LG = LaGeo<LOG2B>;
-    constexpr int B = LG::B, FS = LG::FS, NSL = LG::NSL, JW = LA_JW, NG = LA_NG;
+    constexpr int B = LG::B, FS = LG::FS, NSL = LG::NSL, NG = LA_NG;
     constexpr int ROWB = B * (int)sizeof(float2);
-    static_assert(JW == 2 * NG, "each wave combines two of the slice's steps");
     const ProcJob &J = a.job[0];
     // XCD-aware, as la_anchor_far: the workgroups of one (channel, bin slice)
     // sit 8 apart in the grid, on one XCD
@@ -179,9 +188,9 @@ __global__ __launch_bounds__(LA_NT, 4) void la_batch_walk_kernel(ProcArgs a, LaB
                          RowStream(lab_row<LOG2B>(a, (size_t)c, 0, false), (size_t)LA_BATCH_MAX * ROWB),
                          cur0 + 1 == act ? 0 : cur0 + 1, act};
     float4 *red = reinterpret_cast<float4 *>(smem);  // [NG][JW][FS]
-    // W3, then W2 + W3, of the two steps this wave combines (each entry is
+    // W3, then W2 + W3, of the JW / NG steps this wave combines (each entry is
     // written and read by one thread; in LDS to keep the walk's registers free)
-    float4 *w23 = reinterpret_cast<float4 *>(smem + LabWalk<LOG2B>::red_bytes);
+    float4 *w23 = reinterpret_cast<float4 *>(smem + LabWalk<LOG2B, JW>::red_bytes);
     const int nlv = a.la_nlv;
     // phase 0: level 3, phase 1: level 2 (group l on wave l), phase 2: the
     // level-1 chain (wave 0) and the near chain (wave 1)
@@ -211,8 +220,8 @@ __global__ __launch_bounds__(LA_NT, 4) void la_batch_walk_kernel(ProcArgs a, LaB
         for (int j = 0; j < JW; ++j) red[(l * JW + j) * FS + fl] = acc[j].get();
         __syncthreads();
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int j = 2 * l + t;
+        for (int t = 0; t < JW / NG; ++t) {
+            const int j = (JW / NG) * l + t;
             if (ph < 2) {  // the level's groups in group order, as the anchors combine them
                 float4 p = red[j * FS + fl];
 #pragma unroll

@@ -236,9 +236,14 @@ static hipError_t launch_batch_t(const ProcArgs &a, const LaBatchArgs &b, int ch
                                       LabSpectra<LOG2B>::bytes, s, args, b);
             e != hipSuccess)
             return e;
-        const int wga = LG::NSL * ((b.k + LA_JW - 1) / LA_JW);
-        if (hipError_t e = launch_dyn(la_batch_walk_kernel<LOG2B, FFTCONV_LAB_U>, dim3((channels + 7) / 8 * 8 * wga),
-                                      dim3(LA_NT), LabWalk<LOG2B>::bytes, s, args, b);
+        const bool wide = lab_wide(channels, LG::NSL, b.k);
+        const int wga = LG::NSL * (wide ? (b.k + LAB_JW - 1) / LAB_JW : (b.k + LA_JW - 1) / LA_JW);
+        if (hipError_t e = wide ? launch_dyn(la_batch_walk_kernel<LOG2B, LAB_JW, LAB_U, 2>,
+                                             dim3((channels + 7) / 8 * 8 * wga), dim3(LA_NT),
+                                             LabWalk<LOG2B, LAB_JW>::bytes, s, args, b)
+                                : launch_dyn(la_batch_walk_kernel<LOG2B, LA_JW, LA_UF, 4>,
+                                             dim3((channels + 7) / 8 * 8 * wga), dim3(LA_NT),
+                                             LabWalk<LOG2B, LA_JW>::bytes, s, args, b);
             e != hipSuccess)
             return e;
         if (hipError_t e = launch_dyn(la_batch_finish_kernel<LOG2B>, dim3(channels), dim3(LA_NT),
