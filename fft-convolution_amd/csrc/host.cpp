@@ -2399,18 +2399,21 @@ struct SparseMatrixCore {
     size_t PTmax = 0;     // sum of P_o at active = S (the rows of `part`)
     size_t PT = 0;        // sum of P_o at the current active
     size_t cur = 0, act = 0, fill = 0;
+    size_t last_len = 0;  // response_len of the last init / update: the length update_pairs pads to
     std::vector<int> rowptr, col;  // the host's copy of the pattern
     DevPtr<float2> H, X, pre, part, tw;
     DevPtr<float> ovl, ib, staging;
     DevPtr<int> d_rowptr, d_col, plan;
     DevPtr<int4> wg;      // [PTmax] the MAC workgroups' descriptors, rebuilt with the plan
     hipStream_t stream = nullptr;
+    bool own_stream = true;  // false: a SparseMatrixCrossfadeCore's convolver on its owner's stream
     Scratch scratch;
     PinnedStage hstage;
+    PairLists lists;      // update_pairs (own_stream only: an owner brings its own)
     mutable StreamOrder order;
 
     ~SparseMatrixCore() {
-        if (stream) {
+        if (stream && own_stream) {
             DeviceGuard g(device);
             (void)order.drain(stream);
             (void)hipStreamDestroy(stream);
@@ -2479,6 +2482,7 @@ struct SparseMatrixCore {
         if (int r = wg.alloc(PTmax)) return r;
         if (int r = staging.alloc(N * ir_len)) return r;           // update() never allocates
         if (int r = hstage.alloc(N * ir_len, ir_len)) return r;
+        if (int r = lists.alloc(N)) return r;
         std::vector<float2> t(2 * B);
         const size_t NN = 2 * B;
         for (size_t k = 0; k < NN; ++k) {
@@ -2539,6 +2543,7 @@ struct SparseMatrixCore {
         if (int r = alloc_geometry(dev, inputs, outputs, pairs, max_block, max_len)) return r;
         if (int r = zero_state(stream)) return r;
         if (int r = rebuild_plan(stream)) return r;
+        last_len = len;
         if (S > 0) {
             const bool shared = stride == 0 && N > 1;
             if (len)
@@ -2557,6 +2562,7 @@ struct SparseMatrixCore {
         if (pre.n) HIP_TRY(hipMemsetAsync(pre.p, 0, pre.bytes(), s));   // :187
         if (ovl.n) HIP_TRY(hipMemsetAsync(ovl.p, 0, ovl.bytes(), s));   // :188
         act = ceil_div(len, B);                                     // :190 (current untouched)
+        last_len = len;
         if (int r = rebuild_plan(s)) return r;
         return ir_from_device(src, stride, len, len, s);
     }
@@ -2569,6 +2575,80 @@ struct SparseMatrixCore {
         if (len)
             if (int r = hstage.upload(src, shared ? 1 : N, len, stride, staging.p, ir_len, stream)) return r;
         return update_device(staging.p, shared ? 0 : ir_len, len, stream);
+    }
+
+    // One patch of H (matrix_patch.hip, generic in the pair index: here pair =
+    // the position in the pattern's list, H = [N][S][B]) from the lists staged
+    // in L's mirror, as MatrixCore::patch_device.
+    int patch_device(PairLists &L, size_t n_tr, size_t n_cp, const float2 *Hsrc, const float *src, size_t stride,
+                     bool by_pair, size_t len_data, size_t len_active, hipStream_t s) {
+        if (int r = L.push(n_tr, n_cp, s)) return r;
+        const size_t step = (size_t)kMatrixPatchChunk;
+        for (size_t c0 = 0; c0 < std::max(n_tr, n_cp); c0 += step) {
+            MatrixPatchArgs a{};
+            a.H = H.p;
+            a.Hsrc = Hsrc;
+            a.src = src;
+            a.src_stride = (long long)stride;
+            a.len_data = (long long)len_data;
+            a.len_active = (long long)len_active;
+            a.tw = tw.p;
+            a.tr = L.d.p + c0;
+            a.cp = L.d.p + L.cap + c0;
+            a.n_tr = (int)(c0 < n_tr ? std::min(step, n_tr - c0) : 0);
+            a.n_cp = (int)(c0 < n_cp ? std::min(step, n_cp - c0) : 0);
+            a.row0 = (int)c0;
+            a.by_pair = by_pair ? 1 : 0;
+            a.S = (int)S;
+            a.pairs = (int)N;
+            a.nt_cp = Variant::current().nt_matrix(H.bytes()) ? 1 : 0;
+            HIP_TRY(launch_matrix_patch(log2b, a, s));
+        }
+        return FFTCONV_OK;
+    }
+
+    // the pair list of an update_pairs call as positions in the pattern's list
+    int check_list(size_t n, const uint32_t *pair_out, const uint32_t *pair_in, uint32_t *idx) const {
+        if (n && (!pair_out || !pair_in)) return fail(FFTCONV_E_INVALID, "null pair list");
+        if (n > N) return fail(FFTCONV_E_INVALID, "the pair list must be strictly ascending in (output, input)");
+        size_t bad = 0;
+        const PairListError e = check_pairs_in_pattern(n, pair_out, pair_in, rowptr.data(), col.data(), I, O, idx, &bad);
+        if (e == PAIRS_ABSENT)
+            return fail(FFTCONV_E_INVALID, "pair (" + std::to_string(pair_out[bad]) + ", " + std::to_string(pair_in[bad]) +
+                                               ") is not in the pattern");
+        return e ? pair_list_error(e) : FFTCONV_OK;
+    }
+
+    // update(R'), R' = the responses this matrix holds with the n listed pairs
+    // (list positions, ascending, in L.tr()) replaced by rows 0..n-1 of src, at
+    // the length of the last init / update: update's side effects (the plan
+    // included), and only the listed pairs are transformed.
+    int update_pairs_device(PairLists &L, size_t n, const float *src, size_t stride, size_t len, hipStream_t s) {
+        if (len > last_len)
+            return fail(FFTCONV_E_INVALID, "update_pairs: response longer than the length the response set was applied at");
+        if (ir_len == 0) return FFTCONV_OK;
+        if (pre.n) HIP_TRY(hipMemsetAsync(pre.p, 0, pre.bytes(), s));
+        if (ovl.n) HIP_TRY(hipMemsetAsync(ovl.p, 0, ovl.bytes(), s));
+        act = ceil_div(last_len, B);
+        if (int r = rebuild_plan(s)) return r;
+        return patch_device(L, n, 0, nullptr, src, stride, false, len, last_len, s);
+    }
+    // the C ABI's two variants: d_src == false -- host rows through the pinned staging
+    int update_pairs(size_t n, const uint32_t *pair_out, const uint32_t *pair_in, const float *src, bool d_src,
+                     size_t len, size_t stride, hipStream_t s) {
+        if (int r = check_list(n, pair_out, pair_in, lists.idx.data())) return r;
+        if (len > last_len)
+            return fail(FFTCONV_E_INVALID, "update_pairs: response longer than the length the response set was applied at");
+        DeviceGuard g(device);
+        if (int r = order.enter(s)) return r;
+        if (int r = lists.acquire()) return r;
+        std::copy(lists.idx.begin(), lists.idx.begin() + n, lists.tr());
+        if (!d_src && len && n && ir_len) {
+            const bool shared = stride == 0 && n > 1;
+            if (int r = hstage.upload(src, shared ? 1 : n, len, stride, staging.p, ir_len, s)) return r;
+            return update_pairs_device(lists, n, staging.p, shared ? 0 : ir_len, len, s);
+        }
+        return update_pairs_device(lists, n, src, stride, len, s);
     }
 
     int process_device(const float *din, size_t is, float *dout, size_t os, size_t n, hipStream_t s) {
@@ -2629,16 +2709,24 @@ struct SparseMatrixCore {
         return FFTCONV_OK;
     }
 
-    int clone_from(const SparseMatrixCore &o) {  // #[derive(Clone)]
+    // #[derive(Clone)]; `owner`: the clone is a SparseMatrixCrossfadeCore's
+    // convolver -- it runs on that stream and stages updates through its owner
+    int clone_from(const SparseMatrixCore &o, hipStream_t owner = nullptr) {
         DeviceGuard g(o.device);
         if (int r = o.order.drain(o.stream)) return r;
         device = o.device;
         I = o.I; O = o.O; N = o.N; ir_len = o.ir_len; B = o.B; log2b = o.log2b; S = o.S;
         PTmax = o.PTmax; PT = o.PT;
-        cur = o.cur; act = o.act; fill = o.fill;
+        cur = o.cur; act = o.act; fill = o.fill; last_len = o.last_len;
         rowptr = o.rowptr;
         col = o.col;
-        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        if (owner) {
+            stream = owner;
+            own_stream = false;
+        } else {
+            HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+            if (int r = lists.alloc(N)) return r;
+        }
         auto cp = [&](auto &dst, const auto &src) -> int {
             if (int r = dst.alloc(src.n)) return r;
             if (src.n) HIP_TRY(hipMemcpyAsync(dst.p, src.p, src.bytes(), hipMemcpyDeviceToDevice, stream));
@@ -2656,7 +2744,8 @@ struct SparseMatrixCore {
         if (int r = cp(wg, o.wg)) return r;
         if (int r = part.alloc(o.part.n)) return r;  // (rewritten by every block before it is read)
         if (int r = staging.alloc(o.staging.n)) return r;
-        if (int r = hstage.alloc(o.hstage.n, ir_len)) return r;
+        if (!owner)
+            if (int r = hstage.alloc(o.hstage.n, ir_len)) return r;
         HIP_TRY(hipStreamSynchronize(stream));
         return FFTCONV_OK;
     }
@@ -3067,6 +3156,412 @@ struct MatrixCrossfadeCore {
         HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         a.reset(new (std::nothrow) MatrixCore());
         b.reset(new (std::nothrow) MatrixCore());
+        if (!a || !b) return fail(FFTCONV_E_NOMEM, "out of host memory");
+        if (int r = a->clone_from(*o.a, stream)) return r;
+        if (int r = b->clone_from(*o.b, stream)) return r;
+        if (int r = alloc_buffers(o.hstage.n)) return r;
+        book.copy_from(o.book);
+        if (stored.n) HIP_TRY(hipMemcpyAsync(stored.p, o.stored.p, stored.bytes(), hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return FFTCONV_OK;
+    }
+};
+
+// ---------------------------------------------------------------------------
+// SparseMatrixCrossfadeCore -- N CrossfadeConvolver<FFTConvolver> instances in
+// lockstep, one per listed pair: MatrixCrossfadeCore over two
+// SparseMatrixCores A and B on the handle's stream -- one Crossfader, one
+// response_pending, the mix applied to the per-output sums, the same three
+// paths.  "Pair" is a position in the pattern's list throughout (the PairBook,
+// the lists, the stored response [N][stored_len]).  A copy of the dense core
+// kept honest by the bitwise tests against it; the one difference: a swap that
+// changes the target convolver's active_seg_count rebuilds that convolver's
+// plan on the stream before its next launch.
+// ---------------------------------------------------------------------------
+struct SparseMatrixCrossfadeCore {
+    int device = 0;
+    size_t I = 0, O = 0, N = 0, max_buffer_size = 0, stored_len = 0, stored_stride = 0;
+    size_t stage_row = 0;  // hstage row: the stored response, or a direct update of a / b
+    std::unique_ptr<SparseMatrixCore> a, b;
+    Crossfader xf;
+    DevPtr<float> buf_a, buf_b, stored;  // stored [N][stored_len]
+    DevPtr<float> mix_tab;               // [max_buffer_size + 1] mix_value walk of one call
+    bool response_pending = false;
+    bool in_step = false;  // as MatrixCrossfadeCore: sticky off
+    bool fused = true;     // fftconv_matrix_sparse_crossfade_set_fused
+    bool poisoned = false; // a launch failed between the two convolvers' work
+    hipStream_t stream = nullptr;
+    Scratch scratch;
+    mutable StreamOrder order;
+    PinnedStage hstage;
+    PairBook book;
+    PairLists lists;
+
+    int check_poisoned() const {
+        return poisoned ? fail(FFTCONV_E_DEVICE, "sparse matrix crossfade handle unusable: an earlier process() failed "
+                                                  "between its two convolvers' launches")
+                        : FFTCONV_OK;
+    }
+
+    ~SparseMatrixCrossfadeCore() {
+        if (stream) {
+            DeviceGuard g(device);
+            (void)order.drain(stream);
+            a.reset(); b.reset();  // (they borrow `stream`)
+            (void)hipStreamDestroy(stream);
+        }
+    }
+
+    bool states_agree() const {
+        return a->cur == b->cur && a->act == b->act && a->fill == b->fill && a->act > 0;
+    }
+
+    int alloc_buffers(size_t hstage_count) {
+        if (int r = stored.alloc(N * stored_len)) return r;
+        if (int r = hstage.alloc(hstage_count, stage_row)) return r;
+        if (int r = buf_a.alloc(O * max_buffer_size)) return r;
+        if (int r = buf_b.alloc(O * max_buffer_size)) return r;
+        if (int r = lists.alloc(N)) return r;
+        book.init(N);
+        return mix_tab.alloc(max_buffer_size + 1);
+    }
+
+    // CrossfadeConvolver::new (:19-43)
+    int init_new(const SparseMatrixCore &conv, size_t max_response_length, size_t mbs, size_t crossfade_samples) {
+        if (mbs > (size_t)INT32_MAX) return fail(FFTCONV_E_UNSUPPORTED, "max_buffer_size exceeds 2^31-1");
+        device = conv.device;
+        I = conv.I;
+        O = conv.O;
+        N = conv.N;
+        DeviceGuard g(device);
+        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        a.reset(new (std::nothrow) SparseMatrixCore());
+        b.reset(new (std::nothrow) SparseMatrixCore());
+        if (!a || !b) return fail(FFTCONV_E_NOMEM, "out of host memory");
+        if (int r = a->clone_from(conv, stream)) return r;
+        if (int r = b->clone_from(conv, stream)) return r;
+        in_step = states_agree();
+        stored_len = max_response_length;
+        stored_stride = stored_len;
+        stage_row = std::max(stored_len, a->ir_len);
+        max_buffer_size = mbs;
+        if (int r = alloc_buffers(N * stage_row)) return r;
+        if (stored.n) HIP_TRY(hipMemsetAsync(stored.p, 0, stored.bytes(), stream));
+        xf.init(crossfade_samples, std::min(mbs, max_response_length));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return FFTCONV_OK;
+    }
+
+    int quiesce() const { return order.drain(stream); }
+    bool is_crossfading() const { return xf.approaching; }  // :85-92
+
+    // swap (:94-105) from device samples: update the convolver that is not the
+    // target (its plan included), then fade into it
+    int swap_device(const float *src, size_t stride, size_t len, hipStream_t s) {
+        const int to = xf.target == 0 ? 1 : 0;
+        if (int r = (to ? *b : *a).update_device(src, stride, len, s)) return r;
+        xf.fade_into(to);
+        book.whole_applied();  // every pair of A and B may differ now
+        return FFTCONV_OK;
+    }
+
+    // The partial swap, as MatrixCrossfadeCore::swap_pairs_device: update(R') of
+    // the convolver T that is not the target.  T's active_seg_count becomes
+    // ceil(len_active / B), so its plan is rebuilt behind the stream's earlier
+    // launches and ahead of T's next one.
+    int swap_pairs_device(const uint32_t *lst, size_t n, const float *src, size_t stride, bool by_pair,
+                          size_t len_data, size_t len_active, hipStream_t s) {
+        const int to = xf.target == 0 ? 1 : 0;
+        SparseMatrixCore &t = to ? *b : *a, &other = to ? *a : *b;
+        if (len_active > t.ir_len) return fail(FFTCONV_E_INVALID, "New impulse response is longer than initialized length");
+        if (int r = lists.acquire()) return r;
+        if (n) std::copy(lst, lst + n, lists.tr());
+        const size_t n_cp = book.partial_applied(lst, n, lists.cp());
+        if (t.ir_len != 0) {
+            if (t.pre.n) HIP_TRY(hipMemsetAsync(t.pre.p, 0, t.pre.bytes(), s));   // update's side effects (:186-190)
+            if (t.ovl.n) HIP_TRY(hipMemsetAsync(t.ovl.p, 0, t.ovl.bytes(), s));
+            const size_t act = ceil_div(len_active, t.B);
+            t.last_len = len_active;
+            if (act != t.act) {
+                t.act = act;
+                if (int r = t.rebuild_plan(s)) return r;
+            }
+            if (int r = t.patch_device(lists, n, n_cp, other.H.p, src, stride, by_pair, len_data, len_active, s)) return r;
+        }
+        xf.fade_into(to);
+        return FFTCONV_OK;
+    }
+
+    // the pending response, whole or partial, into the convolver that is not the target
+    int apply_pending(hipStream_t s) {
+        if (!book.partial) return swap_device(stored.p, stored_stride, stored_len, s);
+        const size_t n = book.pending_list(lists.idx.data());
+        if (int r = swap_pairs_device(lists.idx.data(), n, stored.p, stored_len, true, stored_len, stored_len, s)) return r;
+        book.clear_pending();
+        return FFTCONV_OK;
+    }
+
+    // rows k of a listed update (`len` samples each, on the host or the device)
+    // to the stored response's rows lst[k], zero-padded to stored_len
+    int store_rows(const uint32_t *lst, size_t n, const float *src, bool d_src, size_t len, size_t stride, hipStream_t s) {
+        for (size_t k0 = 0; k0 < n;) {
+            size_t k1 = k0 + 1;
+            while (k1 < n && lst[k1] == lst[k1 - 1] + 1) ++k1;
+            float *dst = stored.p + (size_t)lst[k0] * stored_len;
+            if (len < stored_len) HIP_TRY(hipMemsetAsync(dst, 0, (k1 - k0) * stored_len * sizeof(float), s));
+            if (len && d_src) {
+                if (stride >= len) {
+                    HIP_TRY(hipMemcpy2DAsync(dst, stored_len * sizeof(float), src + k0 * stride, stride * sizeof(float),
+                                             len * sizeof(float), k1 - k0, hipMemcpyDeviceToDevice, s));
+                } else {  // (stride 0: one response for every listed pair)
+                    for (size_t k = k0; k < k1; ++k)
+                        HIP_TRY(hipMemcpyAsync(dst + (k - k0) * stored_len, src + k * stride, len * sizeof(float),
+                                               hipMemcpyDeviceToDevice, s));
+                }
+            }
+            k0 = k1;
+        }
+        if (len && !d_src) return hstage.upload_scatter(src, n, len, stride, stored.p, stored_len, lst, s);
+        return FFTCONV_OK;
+    }
+
+    // update_pairs: update(R'), R' = the base set with the listed pairs replaced
+    // (DESIGN §4o, §4p).  `s` is ordered behind the handle's previous work.
+    int update_pairs(size_t n, const uint32_t *pair_out, const uint32_t *pair_in, const float *src, bool d_src,
+                     size_t len, size_t stride, hipStream_t s) {
+        if (int r = check_poisoned()) return r;
+        uint32_t *lst = lists.idx.data();
+        if (int r = a->check_list(n, pair_out, pair_in, lst)) return r;
+        SparseMatrixCore &t = xf.target == 0 ? *b : *a, &base = xf.target == 0 ? *a : *b;
+        const bool fading = is_crossfading();
+        DeviceGuard g(device);
+        if (!fading && !response_pending) {
+            // the base set is the target convolver's, at the length it was applied at
+            const size_t lenp = base.last_len;
+            if (len > lenp)
+                return fail(FFTCONV_E_INVALID, "update_pairs: response longer than the length the response set was applied at");
+            if (int r = order.enter(s)) return r;
+            if (!d_src && len && n && t.ir_len) {
+                const bool shared = stride == 0 && n > 1;
+                if (int r = hstage.upload(src, shared ? 1 : n, len, stride, t.staging.p, t.ir_len, s)) return r;
+                return swap_pairs_device(lst, n, t.staging.p, shared ? 0 : t.ir_len, false, len, lenp, s);
+            }
+            return swap_pairs_device(lst, n, src, stride, false, len, lenp, s);
+        }
+        // the base set is, or becomes, a stored response of stored_len samples
+        if (len > stored_len)
+            return fail(FFTCONV_E_INVALID, fading ? "assertion failed: response_len <= self.stored_response.len()"
+                                                  : "update_pairs: response longer than the stored response");
+        const bool whole = response_pending && !book.partial;
+        if (!whole && ceil_div(stored_len, base.B) != base.act)
+            return fail(FFTCONV_E_UNSUPPORTED, "update_pairs during a fade: the stored length gives another active segment "
+                                               "count than the base convolver's, so zero-padding cannot reproduce update()");
+        if (!fading && stored_len > t.ir_len)
+            return fail(FFTCONV_E_INVALID, "New impulse response is longer than initialized length");
+        if (int r = order.enter(s)) return r;
+        if (whole && stored_stride == 0 && N > 1) {
+            // a shared stored response: every pair gets its own row first
+            for (size_t k = 1; k < N; k *= 2)
+                HIP_TRY(hipMemcpyAsync(stored.p + k * stored_len, stored.p, std::min(k, N - k) * stored_len * sizeof(float),
+                                       hipMemcpyDeviceToDevice, s));
+            stored_stride = stored_len;
+        }
+        if (int r = store_rows(lst, n, src, d_src, len, stride, s)) return r;
+        if (!whole) {
+            book.merge_pending(lst, n);  // (a pair listed twice: the later rows have replaced the earlier ones)
+            stored_stride = stored_len;
+        }
+        response_pending = true;
+        if (!fading) {  // the fade has ended: update(R') swaps at once
+            if (int r = apply_pending(s)) return r;
+            response_pending = false;
+        }
+        return FFTCONV_OK;
+    }
+
+    // Convolution::update (:51-64) from host samples (pair n at src + n * stride,
+    // stride 0 = one response for every pair); staged in pinned memory and
+    // enqueued behind the handle's work: no allocation, no host wait
+    int update_host(const float *src, size_t len, size_t stride) {
+        if (int r = check_poisoned()) return r;
+        DeviceGuard g(device);
+        const bool shared = stride == 0 && N > 1;
+        const size_t rows = shared ? 1 : N;
+        if (!is_crossfading()) {
+            SparseMatrixCore &t = xf.target == 0 ? *b : *a;
+            if (len > t.ir_len) return fail(FFTCONV_E_INVALID, "New impulse response is longer than initialized length");
+            if (int r = order.enter(stream)) return r;
+            if (len)
+                if (int r = hstage.upload(src, rows, len, stride, t.staging.p, t.ir_len, stream)) return r;
+            if (int r = swap_device(t.staging.p, shared ? 0 : t.ir_len, len, stream)) return r;
+            response_pending = false;
+            book.clear_pending();
+            return FFTCONV_OK;
+        }
+        if (len > stored_len) return fail(FFTCONV_E_INVALID, "assertion failed: response_len <= self.stored_response.len()");
+        if (int r = order.enter(stream)) return r;
+        // stored_response[..len] = response; stored_response[len..] = 0
+        if (stored.n) HIP_TRY(hipMemsetAsync(stored.p, 0, stored.bytes(), stream));
+        if (len)
+            if (int r = hstage.upload(src, rows, len, stride, stored.p, stored_len, stream)) return r;
+        stored_stride = shared ? 0 : stored_len;
+        response_pending = true;
+        book.clear_pending();  // (a whole response replaces a pending partial one)
+        return FFTCONV_OK;
+    }
+
+    // Convolution::update (:51-64) from device samples, stream-ordered (the
+    // caller has ordered s behind the handle's previous work)
+    int update_device(const float *src, size_t len, size_t stride, hipStream_t s) {
+        if (int r = check_poisoned()) return r;
+        if (!is_crossfading()) {
+            if (int r = swap_device(src, stride, len, s)) return r;
+            response_pending = false;
+            book.clear_pending();
+            return FFTCONV_OK;
+        }
+        if (len > stored_len) return fail(FFTCONV_E_INVALID, "assertion failed: response_len <= self.stored_response.len()");
+        const bool shared = stride == 0 && N > 1;
+        if (stored.n) HIP_TRY(hipMemsetAsync(stored.p, 0, stored.bytes(), s));
+        if (len)
+            HIP_TRY(hipMemcpy2DAsync(stored.p, stored_len * sizeof(float), src, (shared ? len : std::max(stride, len)) * sizeof(float),
+                                     len * sizeof(float), shared ? 1 : N, hipMemcpyDeviceToDevice, s));
+        stored_stride = shared ? 0 : stored_len;
+        response_pending = true;
+        book.clear_pending();  // (a whole response replaces a pending partial one)
+        return FFTCONV_OK;
+    }
+
+    CrossfadeMixArgs mix_args(float *dout, size_t os, size_t out_len) const {
+        CrossfadeMixArgs x{};
+        x.buf_a = buf_a.p; x.buf_b = buf_b.p; x.buf_stride = (long long)max_buffer_size;
+        x.out = dout; x.out_stride = (long long)os; x.n = (int)out_len;
+        x.approaching = xf.approaching ? 1 : 0; x.target = xf.target;
+        x.counter0 = xf.counter; x.fading = xf.fading_samples;
+        x.mix_value0 = xf.mix_value; x.step = xf.mix_value_step;
+        return x;
+    }
+
+    // 0 = composition, 1 = fused with both convolvers live, 2 = fused with one
+    // idle: a function of the handle's state only
+    int path_now() const {
+        if (!fused || !in_step || !states_agree()) return 0;
+        return xf.approaching ? 1 : 2;
+    }
+    // the path the next process() takes: a pending swap is applied first, and
+    // the path follows from the target convolver's NEW active_seg_count
+    int path_next() const {
+        if (!is_crossfading() && response_pending) {
+            const SparseMatrixCore &t = xf.target == 0 ? *b : *a, &other = xf.target == 0 ? *a : *b;
+            if (t.ir_len == 0 || stored_len > t.ir_len) return path_now();  // (the update changes nothing)
+            const size_t act = ceil_div(stored_len, t.B);
+            return fused && in_step && act > 0 && act == other.act && t.cur == other.cur && t.fill == other.fill ? 1 : 0;
+        }
+        return path_now();
+    }
+
+    // Convolution::process (:66-78): both convolvers advance by max_buffer_size
+    // samples, the first out_len mixed samples are written
+    int process_device(const float *din, size_t is, float *dout, size_t os, size_t out_len, hipStream_t s) {
+        if (int r = check_poisoned()) return r;
+        if (out_len > max_buffer_size) return fail(FFTCONV_E_INVALID, "output longer than max_buffer_size (index out of bounds)");
+        if (!is_crossfading() && response_pending) {                    // :67-70
+            if (int r = apply_pending(s)) return r;
+            response_pending = false;
+        }
+        const size_t m = max_buffer_size;
+        if (m == 0) return FFTCONV_OK;
+        in_step = in_step && states_agree();
+        CrossfadeMixArgs mx = mix_args(dout, os, out_len);
+        if (path_now() == 0) {
+            if (int r = a->process_device(din, is, buf_a.p, m, m, s)) return r;    // :72
+            if (int r = b->process_device(din, is, buf_b.p, m, m, s)) {            // :73
+                poisoned = true;
+                return r;
+            }
+            if (out_len > 1024 && mx.approaching) {
+                HIP_TRY(launch_crossfade_walk(mx, mix_tab.p, s));
+                mx.vtab = mix_tab.p;
+            }
+            HIP_TRY(launch_crossfade_mix(mx, (int)O, s));                          // :75-77
+            xf.advance(out_len);
+            return FFTCONV_OK;
+        }
+        if (mx.approaching) mx.vtab = mix_tab.p;  // the call's mix_value walk: launch A of the first chunk fills it
+        MatrixSpXfArgs x{};
+        const SparseMatrixCore *cv[2] = {a.get(), b.get()};
+        for (int c = 0; c < 2; ++c) {
+            x.H[c] = cv[c]->H.p; x.X[c] = cv[c]->X.p; x.ovl[c] = cv[c]->ovl.p; x.ib[c] = cv[c]->ib.p;
+            x.pre[c] = cv[c]->pre.p; x.part[c] = cv[c]->part.p;
+        }
+        // (in step: A and B have the same active_seg_count, so their plans are equal)
+        x.rowptr = a->d_rowptr.p; x.col = a->d_col.p; x.plan = a->plan.p; x.wg = a->wg.p;
+        x.tw = a->tw.p;
+        x.in_stride = (long long)is;
+        x.out_stride = (long long)os;
+        x.I = (int)I; x.O = (int)O; x.S = (int)a->S; x.N = (int)N;
+        x.PT = (int)a->PT;
+        x.act = (int)a->act;
+        x.nt_h = Variant::current().nt_matrix(a->H.bytes()) ? 1 : 0;
+        x.live = xf.approaching ? 3 : (xf.target == 0 ? 1 : 2);
+        x.mix = mx;
+        const size_t B = a->B;
+        size_t processed = 0;
+        while (processed < m) {                                         // FFTConvolver::process :222-294, A and B at once
+            const size_t k = std::min(m - processed, B - a->fill);
+            x.in = din + processed;
+            x.out = dout + processed;
+            x.cur = (int)a->cur;
+            x.fill = (int)a->fill;
+            x.k = (int)k;
+            x.off = (int)processed;
+            x.walk = processed == 0 && mx.approaching ? mix_tab.p : nullptr;
+            if (hipError_t e = launch_matrix_sp_xf_chunk(a->log2b, x, s); e != hipSuccess) {
+                poisoned = true;
+                HIP_TRY(e);
+            }
+            a->fill += k;
+            if (a->fill == B) {
+                a->fill = 0;
+                a->cur = a->cur > 0 ? a->cur - 1 : a->act - 1;
+            }
+            b->fill = a->fill;
+            b->cur = a->cur;
+            processed += k;
+        }
+        xf.advance(out_len);
+        return FFTCONV_OK;
+    }
+
+    int process_host(const float *in, size_t in_len, float *out, size_t out_len) {
+        if (in_len < max_buffer_size) return fail(FFTCONV_E_INVALID, "input shorter than max_buffer_size (range end index out of range)");
+        if (out_len > max_buffer_size) return fail(FFTCONV_E_INVALID, "output longer than max_buffer_size (index out of bounds)");
+        if (int r = check_poisoned()) return r;
+        DeviceGuard g(device);
+        if (int r = order.enter(stream)) return r;
+        const size_t m = max_buffer_size, on = std::max<size_t>(out_len, 1);
+        if (int r = scratch.ensure(I * std::max<size_t>(m, 1), O * on)) return r;
+        if (m)
+            HIP_TRY(hipMemcpy2DAsync(scratch.in.p, m * sizeof(float), in, in_len * sizeof(float), m * sizeof(float), I,
+                                     hipMemcpyHostToDevice, stream));
+        if (int r = process_device(scratch.in.p, m, scratch.out.p, on, out_len, stream)) return r;
+        if (out_len && m)
+            HIP_TRY(hipMemcpy2DAsync(out, out_len * sizeof(float), scratch.out.p, on * sizeof(float),
+                                     out_len * sizeof(float), O, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return FFTCONV_OK;
+    }
+
+    int clone_from(const SparseMatrixCrossfadeCore &o) {
+        DeviceGuard g(o.device);
+        if (int r = o.order.drain(o.stream)) return r;
+        device = o.device; I = o.I; O = o.O; N = o.N; max_buffer_size = o.max_buffer_size;
+        stored_len = o.stored_len; stored_stride = o.stored_stride; stage_row = o.stage_row;
+        xf = o.xf; response_pending = o.response_pending;
+        in_step = o.in_step; fused = o.fused; poisoned = o.poisoned;
+        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        a.reset(new (std::nothrow) SparseMatrixCore());
+        b.reset(new (std::nothrow) SparseMatrixCore());
         if (!a || !b) return fail(FFTCONV_E_NOMEM, "out of host memory");
         if (int r = a->clone_from(*o.a, stream)) return r;
         if (int r = b->clone_from(*o.b, stream)) return r;
@@ -3652,6 +4147,7 @@ struct fftconv_matrix { MatrixCore core; };
 struct fftconv_matrix_sparse { SparseMatrixCore core; };
 struct fftconv_matrix_lookahead { MatrixLookaheadCore core; };
 struct fftconv_matrix_crossfade { MatrixCrossfadeCore core; };
+struct fftconv_matrix_sparse_crossfade { SparseMatrixCrossfadeCore core; };
 struct fftconv_matrix_twostage { MatrixTwoStageCore core; };
 
 extern "C" {
@@ -4197,6 +4693,20 @@ int fftconv_matrix_sparse_update_device(fftconv_matrix_sparse *h, const float *d
     if (int r = h->core.order.enter(s)) return r;
     return h->core.update_device(d_responses, response_stride, response_len, s);
 }
+int fftconv_matrix_sparse_update_pairs(fftconv_matrix_sparse *h, size_t n_pairs, const uint32_t *pair_out,
+                                       const uint32_t *pair_in, const float *responses, size_t response_len,
+                                       size_t response_stride) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.update_pairs(n_pairs, pair_out, pair_in, responses, false, response_len, response_stride,
+                                h->core.stream);
+}
+int fftconv_matrix_sparse_update_pairs_device(fftconv_matrix_sparse *h, size_t n_pairs, const uint32_t *pair_out,
+                                              const uint32_t *pair_in, const float *d_responses, size_t response_len,
+                                              size_t response_stride, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.update_pairs(n_pairs, pair_out, pair_in, d_responses, true, response_len, response_stride,
+                                (hipStream_t)hip_stream);
+}
 int fftconv_matrix_sparse_reset(fftconv_matrix_sparse *h) {
     if (!h) return fail(FFTCONV_E_INVALID, "null handle");
     DeviceGuard g(h->core.device);
@@ -4360,6 +4870,129 @@ int fftconv_matrix_crossfade_set_fused(fftconv_matrix_crossfade *h, int on) {
     return FFTCONV_OK;
 }
 int fftconv_matrix_crossfade_path(const fftconv_matrix_crossfade *h) { return h ? h->core.path_next() : 0; }
+
+// ---- sparse matrix crossfade ---------------------------------------
+fftconv_matrix_sparse_crossfade *fftconv_matrix_sparse_crossfade_init(int device, size_t inputs, size_t outputs,
+                                                                      size_t pairs, const uint32_t *pair_out,
+                                                                      const uint32_t *pair_in, const float *responses,
+                                                                      size_t response_len, size_t response_stride,
+                                                                      size_t max_block_size,
+                                                                      size_t max_response_length) {
+    fftconv_matrix_sparse *conv = fftconv_matrix_sparse_init(device, inputs, outputs, pairs, pair_out, pair_in, responses,
+                                                             response_len, response_stride, max_block_size,
+                                                             max_response_length);
+    if (!conv) return nullptr;
+    // Convolution::init (src/crossfade_convolver.rs:46-49)
+    fftconv_matrix_sparse_crossfade *h =
+        fftconv_matrix_sparse_crossfade_new(conv, response_len, max_block_size, response_len);
+    fftconv_matrix_sparse_destroy(conv);
+    return h;
+}
+fftconv_matrix_sparse_crossfade *fftconv_matrix_sparse_crossfade_new(const fftconv_matrix_sparse *convolver,
+                                                                     size_t max_response_length,
+                                                                     size_t max_buffer_size,
+                                                                     size_t crossfade_samples) {
+    if (!convolver) { set_error("null handle"); return nullptr; }
+    auto *h = new (std::nothrow) fftconv_matrix_sparse_crossfade();
+    if (!h) { set_error("out of host memory"); return nullptr; }
+    return make_or_null(h->core.init_new(convolver->core, max_response_length, max_buffer_size, crossfade_samples), h);
+}
+int fftconv_matrix_sparse_crossfade_update(fftconv_matrix_sparse_crossfade *h, const float *responses,
+                                           size_t response_len, size_t response_stride) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.update_host(responses, response_len, response_stride);
+}
+int fftconv_matrix_sparse_crossfade_update_device(fftconv_matrix_sparse_crossfade *h, const float *d_responses,
+                                                  size_t response_len, size_t response_stride, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.device);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int r = h->core.order.enter(s)) return r;
+    return h->core.update_device(d_responses, response_len, response_stride, s);
+}
+int fftconv_matrix_sparse_crossfade_update_pairs(fftconv_matrix_sparse_crossfade *h, size_t n_pairs,
+                                                 const uint32_t *pair_out, const uint32_t *pair_in,
+                                                 const float *responses, size_t response_len,
+                                                 size_t response_stride) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.update_pairs(n_pairs, pair_out, pair_in, responses, false, response_len, response_stride,
+                                h->core.stream);
+}
+int fftconv_matrix_sparse_crossfade_update_pairs_device(fftconv_matrix_sparse_crossfade *h, size_t n_pairs,
+                                                        const uint32_t *pair_out, const uint32_t *pair_in,
+                                                        const float *d_responses, size_t response_len,
+                                                        size_t response_stride, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.update_pairs(n_pairs, pair_out, pair_in, d_responses, true, response_len, response_stride,
+                                (hipStream_t)hip_stream);
+}
+size_t fftconv_matrix_sparse_crossfade_diff_pairs(const fftconv_matrix_sparse_crossfade *h) {
+    return h ? h->core.book.nd : 0;
+}
+int fftconv_matrix_sparse_crossfade_last_patch(const fftconv_matrix_sparse_crossfade *h, size_t out2[2]) {
+    if (!h || !out2) return fail(FFTCONV_E_INVALID, "null handle");
+    out2[0] = h->core.book.last[0];
+    out2[1] = h->core.book.last[1];
+    return FFTCONV_OK;
+}
+int fftconv_matrix_sparse_crossfade_reset(fftconv_matrix_sparse_crossfade *h) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return fail(FFTCONV_E_UNIMPLEMENTED, "not yet implemented (CrossfadeConvolver::reset is todo!())");
+}
+int fftconv_matrix_sparse_crossfade_process(fftconv_matrix_sparse_crossfade *h, const float *input, size_t input_len,
+                                            float *output, size_t output_len) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.process_host(input, input_len, output, output_len);
+}
+int fftconv_matrix_sparse_crossfade_process_device(fftconv_matrix_sparse_crossfade *h, const float *d_input,
+                                                   size_t in_stride, float *d_output, size_t out_stride,
+                                                   size_t output_len, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.device);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int r = h->core.order.enter(s)) return r;
+    return h->core.process_device(d_input, in_stride, d_output, out_stride, output_len, s);
+}
+int fftconv_matrix_sparse_crossfade_process_device_steps(fftconv_matrix_sparse_crossfade *h, const float *d_input,
+                                                         size_t in_stride, size_t in_step, float *d_output,
+                                                         size_t out_stride, size_t out_step, size_t output_len,
+                                                         size_t steps, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.device);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int r = h->core.order.enter(s)) return r;
+    for (size_t k = 0; k < steps; ++k)
+        if (int r = h->core.process_device(d_input + k * in_step, in_stride, d_output + k * out_step, out_stride,
+                                           output_len, s))
+            return r;
+    return FFTCONV_OK;
+}
+int fftconv_matrix_sparse_crossfade_is_crossfading(const fftconv_matrix_sparse_crossfade *h) {
+    return h && h->core.is_crossfading() ? 1 : 0;
+}
+fftconv_matrix_sparse_crossfade *fftconv_matrix_sparse_crossfade_clone(const fftconv_matrix_sparse_crossfade *h) {
+    if (!h) { set_error("null handle"); return nullptr; }
+    auto *c = new (std::nothrow) fftconv_matrix_sparse_crossfade();
+    if (!c) { set_error("out of host memory"); return nullptr; }
+    return make_or_null(c->core.clone_from(h->core), c);
+}
+void fftconv_matrix_sparse_crossfade_destroy(fftconv_matrix_sparse_crossfade *h) { delete h; }
+int fftconv_matrix_sparse_crossfade_synchronize(fftconv_matrix_sparse_crossfade *h) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.device);
+    return h->core.quiesce();
+}
+size_t fftconv_matrix_sparse_crossfade_inputs(const fftconv_matrix_sparse_crossfade *h) { return h ? h->core.I : 0; }
+size_t fftconv_matrix_sparse_crossfade_outputs(const fftconv_matrix_sparse_crossfade *h) { return h ? h->core.O : 0; }
+size_t fftconv_matrix_sparse_crossfade_pairs(const fftconv_matrix_sparse_crossfade *h) { return h ? h->core.N : 0; }
+int fftconv_matrix_sparse_crossfade_set_fused(fftconv_matrix_sparse_crossfade *h, int on) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    h->core.fused = on != 0;
+    return FFTCONV_OK;
+}
+int fftconv_matrix_sparse_crossfade_path(const fftconv_matrix_sparse_crossfade *h) {
+    return h ? h->core.path_next() : 0;
+}
 
 // ---- matrix two-stage ---------------------------------------------
 fftconv_matrix_twostage *fftconv_matrix_twostage_init(int device, size_t inputs, size_t outputs,

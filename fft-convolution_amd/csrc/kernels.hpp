@@ -503,6 +503,37 @@ struct MatrixXfArgs {
 // the chunk's two launches (32 <= B <= 8192)
 hipError_t launch_matrix_xf_chunk(int log2b, const MatrixXfArgs &a, hipStream_t s);
 
+// SparseMatrixCrossfadeConvolver (matrix_sp_xf.hip): one chunk of
+// the two sparse matrices A and B of a crossfaded handle while they are in step
+// -- MatrixXfArgs over the CSR pattern of MatrixSpArgs.  A and B have the same
+// active_seg_count, so ONE plan serves both (A's).  [0] = A, [1] = B.
+struct MatrixSpXfArgs {
+    const float2 *H[2];    // [N][S][B] each
+    float2 *X[2];          // [I][S][B] each; the chunk's row is written to both
+    float *ovl[2];         // [O][B]
+    float *ib[2];          // [I][B]; both maintained
+    float2 *pre[2];        // [O][B]
+    float2 *part[2];       // [sum P_o][B]
+    const int *rowptr;     // as MatrixSpArgs
+    const int *col;
+    const int *plan;
+    const int4 *wg;
+    const float2 *tw;      // W_N^k, k < N = 2B
+    const float *in;       // chunk of input 0 (+ in_stride per input)
+    long long in_stride;
+    float *out;            // chunk of output 0 (+ out_stride per output)
+    long long out_stride;
+    int I, O, S, N;
+    int PT;                // plan[O]
+    int cur, act, fill, k;
+    int nt_h;              // nontemporal H streams (Variant::nt_matrix of one H)
+    int live, off;         // as MatrixXfArgs
+    CrossfadeMixArgs mix;
+    float *walk;
+};
+// the chunk's two launches (32 <= B <= 8192)
+hipError_t launch_matrix_sp_xf_chunk(int log2b, const MatrixSpXfArgs &a, hipStream_t s);
+
 // update_pairs (matrix_patch.hip): patch the spectra H of one matrix
 // for listed pairs (pair = o * I + i) in one launch -- the pairs of `tr` are
 // transformed from their response rows (the bits launch_ir_segments writes),

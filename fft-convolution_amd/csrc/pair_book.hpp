@@ -12,7 +12,7 @@
 
 namespace fftconv {
 
-enum PairListError { PAIRS_OK = 0, PAIRS_RANGE = 1, PAIRS_ORDER = 2 };
+enum PairListError { PAIRS_OK = 0, PAIRS_RANGE = 1, PAIRS_ORDER = 2, PAIRS_ABSENT = 3 };
 
 // pairs (pair_out[n], pair_in[n]) must be in range and strictly ascending in
 // o * I + i (so: no repeats); idx[n] = o * I + i (room for O * I entries)
@@ -25,6 +25,32 @@ inline PairListError check_pairs(size_t n, const uint32_t *pair_out, const uint3
         if (k > 0 && p <= prev) return PAIRS_ORDER;  // (strictly ascending and in range: k < O * I)
         idx[k] = (uint32_t)p;
         prev = p;
+    }
+    return PAIRS_OK;
+}
+
+// check_pairs for a sparse matrix's update_pairs: the pairs must be in range,
+// strictly ascending in (o, i) and belong to the CSR pattern (rowptr[O + 1],
+// col[N], each row's inputs ascending); idx[n] = the pair's position in the
+// pattern's list (room for N entries).  *bad = the first offending entry.
+inline PairListError check_pairs_in_pattern(size_t n, const uint32_t *pair_out, const uint32_t *pair_in,
+                                            const int *rowptr, const int *col, size_t I, size_t O, uint32_t *idx,
+                                            size_t *bad = nullptr) {
+    for (size_t k = 0; k < n; ++k) {
+        if (bad) *bad = k;
+        const uint32_t o = pair_out[k], i = pair_in[k];
+        if (o >= O || i >= I) return PAIRS_RANGE;
+        if (k > 0 && (o < pair_out[k - 1] || (o == pair_out[k - 1] && i <= pair_in[k - 1]))) return PAIRS_ORDER;
+        int lo = rowptr[o], hi = rowptr[o + 1];  // (binary search of output o's row)
+        while (lo < hi) {
+            const int mid = lo + (hi - lo) / 2;
+            if ((uint32_t)col[mid] < i)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        if (lo >= rowptr[o + 1] || (uint32_t)col[lo] != i) return PAIRS_ABSENT;
+        idx[k] = (uint32_t)lo;  // (ascending and in the pattern: k < N)
     }
     return PAIRS_OK;
 }

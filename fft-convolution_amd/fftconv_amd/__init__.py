@@ -144,6 +144,8 @@ SIGNATURES = {
     "fftconv_matrix_sparse_init": (_vp, [_i, _sz, _sz, _sz, _u32p, _u32p, _fp, _sz, _sz, _sz, _sz]),
     "fftconv_matrix_sparse_update": (_i, [_vp, _fp, _sz, _sz]),
     "fftconv_matrix_sparse_update_device": (_i, [_vp, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_sparse_update_pairs": (_i, [_vp, _sz, _u32p, _u32p, _fp, _sz, _sz]),
+    "fftconv_matrix_sparse_update_pairs_device": (_i, [_vp, _sz, _u32p, _u32p, _vp, _sz, _sz, _vp]),
     "fftconv_matrix_sparse_reset": (_i, [_vp]),
     "fftconv_matrix_sparse_process": (_i, [_vp, _fp, _sz, _fp, _sz]),
     "fftconv_matrix_sparse_process_device": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _vp]),
@@ -178,6 +180,27 @@ SIGNATURES = {
     "fftconv_matrix_crossfade_outputs": (_sz, [_vp]),
     "fftconv_matrix_crossfade_set_fused": (_i, [_vp, _i]),
     "fftconv_matrix_crossfade_path": (_i, [_vp]),
+    "fftconv_matrix_sparse_crossfade_init": (_vp, [_i, _sz, _sz, _sz, _u32p, _u32p, _fp, _sz, _sz, _sz, _sz]),
+    "fftconv_matrix_sparse_crossfade_new": (_vp, [_vp, _sz, _sz, _sz]),
+    "fftconv_matrix_sparse_crossfade_update": (_i, [_vp, _fp, _sz, _sz]),
+    "fftconv_matrix_sparse_crossfade_update_device": (_i, [_vp, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_sparse_crossfade_update_pairs": (_i, [_vp, _sz, _u32p, _u32p, _fp, _sz, _sz]),
+    "fftconv_matrix_sparse_crossfade_update_pairs_device": (_i, [_vp, _sz, _u32p, _u32p, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_sparse_crossfade_diff_pairs": (_sz, [_vp]),
+    "fftconv_matrix_sparse_crossfade_last_patch": (_i, [_vp, C.POINTER(_sz)]),
+    "fftconv_matrix_sparse_crossfade_reset": (_i, [_vp]),
+    "fftconv_matrix_sparse_crossfade_process": (_i, [_vp, _fp, _sz, _fp, _sz]),
+    "fftconv_matrix_sparse_crossfade_process_device": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_sparse_crossfade_process_device_steps": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _sz, _sz, _vp]),
+    "fftconv_matrix_sparse_crossfade_is_crossfading": (_i, [_vp]),
+    "fftconv_matrix_sparse_crossfade_clone": (_vp, [_vp]),
+    "fftconv_matrix_sparse_crossfade_destroy": (None, [_vp]),
+    "fftconv_matrix_sparse_crossfade_synchronize": (_i, [_vp]),
+    "fftconv_matrix_sparse_crossfade_inputs": (_sz, [_vp]),
+    "fftconv_matrix_sparse_crossfade_outputs": (_sz, [_vp]),
+    "fftconv_matrix_sparse_crossfade_pairs": (_sz, [_vp]),
+    "fftconv_matrix_sparse_crossfade_set_fused": (_i, [_vp, _i]),
+    "fftconv_matrix_sparse_crossfade_path": (_i, [_vp]),
     "fftconv_matrix_twostage_init": (_vp, [_i, _sz, _sz, _fp, _sz, _sz, _sz, _sz]),
     "fftconv_matrix_twostage_update": (_i, [_vp, _fp, _sz, _sz]),
     "fftconv_matrix_twostage_reset": (_i, [_vp]),
@@ -594,7 +617,7 @@ def _pair_arrays(pairs):
 
 
 class _UpdatePairs:
-    """update_pairs of the dense and the crossfaded matrix (fftconv.h): update(R'),
+    """update_pairs of the dense, sparse and crossfaded matrices (fftconv.h): update(R'),
     R' = the responses the handle holds with the listed pairs replaced."""
 
     def update_pairs(self, pairs, responses):
@@ -782,7 +805,7 @@ class MatrixLookaheadConvolver(_Base):
         return tuple(int(v) for v in out)
 
 
-class SparseMatrixConvolver(_Base):
+class SparseMatrixConvolver(_UpdatePairs, _Base):
     """Matrix convolution over a listed pair set (fftconv.h,
     "SparseMatrixConvolver"): one FFTConvolver instance per listed (output,
     input) pair, in lockstep; output o is the sum of the instances listed for
@@ -791,11 +814,12 @@ class SparseMatrixConvolver(_Base):
 
     _prefix = "matrix_sparse"
 
-    def __init__(self, h, inputs: int, outputs: int, pairs: int):
+    def __init__(self, h, inputs: int, outputs: int, pairs: int, pair_list=None):
         super().__init__(h, inputs)
         self.inputs = inputs
         self.outputs = outputs
         self.pairs = pairs
+        self._pair_list = [(int(o), int(i)) for o, i in pair_list] if pair_list is not None else None
 
     def _rows(self, responses):
         r = _f32(responses)
@@ -820,7 +844,7 @@ class SparseMatrixConvolver(_Base):
         h = lib().fftconv_matrix_sparse_init(device, inputs, outputs, len(pr), po.ctypes.data_as(_u32p),
                                              pi.ctypes.data_as(_u32p), _p(r), n, n, max_block_size,
                                              max_response_length)
-        return cls(_handle(h), inputs, outputs, len(pr))
+        return cls(_handle(h), inputs, outputs, len(pr), pr.tolist())
 
     def update(self, responses):
         """update() of every listed pair with responses[pairs][len] (whole matrix only)."""
@@ -849,7 +873,7 @@ class SparseMatrixConvolver(_Base):
 
     def clone(self):
         return SparseMatrixConvolver(_handle(lib().fftconv_matrix_sparse_clone(self._h)), self.inputs, self.outputs,
-                                     self.pairs)
+                                     self.pairs, self._pair_list)
 
     @property
     def block_size(self) -> int:
@@ -960,6 +984,116 @@ class MatrixCrossfadeConvolver(_UpdatePairs, _Base):
         """The path the next process() takes: 0 composition, 1 fused with both
         convolvers live, 2 fused with one convolver idle."""
         return int(lib().fftconv_matrix_crossfade_path(self._h))
+
+
+class SparseMatrixCrossfadeConvolver(_UpdatePairs, _Base):
+    """Crossfaded response switching for the sparse matrix (fftconv.h,
+    "SparseMatrixCrossfadeConvolver"): one CrossfadeConvolver<FFTConvolver>
+    instance per listed (output, input) pair, in lockstep, one crossfader, the
+    mix applied to the per-output sums; update_pairs takes listed pairs."""
+
+    _prefix = "matrix_sparse_crossfade"
+
+    def __init__(self, h, inputs: int, outputs: int, pair_list, max_buffer_size: int):
+        super().__init__(h, inputs)
+        self.inputs = inputs
+        self.outputs = outputs
+        self._pair_list = [(int(o), int(i)) for o, i in pair_list]
+        self.pairs = len(self._pair_list)
+        self.max_buffer_size = max_buffer_size
+
+    def _rows(self, responses):
+        r = _f32(responses)
+        if r.ndim != 2 or r.shape[0] != self.pairs:
+            raise ValueError("responses must be [pairs][len]")
+        return r
+
+    @classmethod
+    def init(cls, pairs, responses, inputs: int, outputs: int, max_block_size: int, max_response_length: int,
+             device: int = 0):
+        """Convolution::init (:46-49) over the listed pairs ((output, input)
+        tuples, strictly ascending; responses[n] is the response of pairs[n]):
+        the fade takes len samples, the hold min(max_block_size, len)."""
+        po, pi = _pair_arrays(pairs)
+        r = _f32(responses)
+        if r.ndim != 2 or r.shape[0] != len(po):
+            raise ValueError("responses must be [pairs][len]")
+        n = r.shape[1]
+        h = lib().fftconv_matrix_sparse_crossfade_init(device, inputs, outputs, len(po), po.ctypes.data_as(_u32p),
+                                                       pi.ctypes.data_as(_u32p), _p(r), n, n, max_block_size,
+                                                       max_response_length)
+        return cls(_handle(h), inputs, outputs, list(zip(po.tolist(), pi.tolist())), max_block_size)
+
+    @classmethod
+    def new(cls, convolver: SparseMatrixConvolver, max_response_length: int, max_buffer_size: int,
+            crossfade_samples: int):
+        """CrossfadeConvolver::new (:19-43); the SparseMatrixConvolver is cloned."""
+        if not isinstance(convolver, SparseMatrixConvolver):
+            raise TypeError("convolver must be a SparseMatrixConvolver")
+        h = lib().fftconv_matrix_sparse_crossfade_new(convolver._h, max_response_length, max_buffer_size,
+                                                      crossfade_samples)
+        return cls(_handle(h), convolver.inputs, convolver.outputs, convolver._pair_list, max_buffer_size)
+
+    def update(self, responses):
+        """update() of every listed pair with responses[pairs][len] (:51-64):
+        starts the fade, or is stored until the fade under way has ended."""
+        r = self._rows(responses)
+        _check(lib().fftconv_matrix_sparse_crossfade_update(self._h, _p(r), r.shape[1], r.shape[1]))
+
+    def update_device(self, d_responses: int, response_len: int, stride: int = 0, stream: int = 0):
+        """update() from device memory (pair n, in list order, at d_responses +
+        4 * n * stride; stride 0 = one response for every pair), stream-ordered."""
+        _check(self._fn("update_device")(self._h, C.c_void_p(d_responses), response_len, stride,
+                                         C.c_void_p(stream) if stream else None))
+
+    def update_input(self, i: int, responses):
+        """update_pairs of the listed pairs that read input i, in list order."""
+        self.update_pairs([p for p in self._pair_list if p[1] == i], responses)
+
+    def update_output(self, o: int, responses):
+        """update_pairs of the listed pairs that feed output o, in list order."""
+        self.update_pairs([p for p in self._pair_list if p[0] == o], responses)
+
+    def diff_pairs(self) -> int:
+        """|D|: the listed pairs whose spectra may differ between the two convolvers."""
+        return int(lib().fftconv_matrix_sparse_crossfade_diff_pairs(self._h))
+
+    def last_patch(self):
+        """(pairs transformed, pairs copied) by the last applied swap."""
+        out = (C.c_size_t * 2)()
+        _check(lib().fftconv_matrix_sparse_crossfade_last_patch(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def reset(self):
+        _check(lib().fftconv_matrix_sparse_crossfade_reset(self._h))
+
+    def process(self, inp, out_len: int | None = None) -> np.ndarray:
+        """x[inputs][n >= max_buffer_size] -> y[outputs][out_len or n]; the state
+        advances by max_buffer_size samples whatever out_len is."""
+        x = _f32(inp)
+        if x.ndim != 2 or x.shape[0] != self.inputs:
+            raise ValueError(f"input must be [{self.inputs}][n]")
+        n_in = x.shape[1]
+        n = n_in if out_len is None else out_len
+        y = np.zeros((self.outputs, n), np.float32)
+        _check(lib().fftconv_matrix_sparse_crossfade_process(self._h, _p(x), n_in, _p(y), n))
+        return y
+
+    def is_crossfading(self) -> bool:
+        return bool(lib().fftconv_matrix_sparse_crossfade_is_crossfading(self._h))
+
+    def clone(self):
+        return SparseMatrixCrossfadeConvolver(_handle(lib().fftconv_matrix_sparse_crossfade_clone(self._h)),
+                                              self.inputs, self.outputs, self._pair_list, self.max_buffer_size)
+
+    def set_fused(self, on: bool):
+        """False: every call takes the composition path (tests, A/B runs)."""
+        _check(lib().fftconv_matrix_sparse_crossfade_set_fused(self._h, 1 if on else 0))
+
+    def path(self) -> int:
+        """The path the next process() takes: 0 composition, 1 fused with both
+        convolvers live, 2 fused with one convolver idle."""
+        return int(lib().fftconv_matrix_sparse_crossfade_path(self._h))
 
 
 class MatrixTwoStageConvolver(_Base):

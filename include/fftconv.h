@@ -63,6 +63,7 @@ typedef struct fftconv_twostage fftconv_twostage;   /* TwoStageFFTConvolver src/
 typedef struct fftconv_crossfade fftconv_crossfade; /* CrossfadeConvolver<FFTConvolver | TwoStageFFTConvolver> src/crossfade_convolver.rs:10-105 */
 typedef struct fftconv_matrix fftconv_matrix;       /* inputs x outputs FFTConvolver instances, summed per output (below) */
 typedef struct fftconv_matrix_sparse fftconv_matrix_sparse; /* one FFTConvolver instance per listed (output, input) pair (below) */
+typedef struct fftconv_matrix_sparse_crossfade fftconv_matrix_sparse_crossfade; /* one CrossfadeConvolver per listed pair (below) */
 typedef struct fftconv_matrix_lookahead fftconv_matrix_lookahead; /* the matrix with far-row windows (below) */
 typedef struct fftconv_matrix_crossfade fftconv_matrix_crossfade; /* inputs x outputs CrossfadeConvolver<FFTConvolver> instances (below) */
 typedef struct fftconv_matrix_twostage fftconv_matrix_twostage;   /* inputs x outputs TwoStageFFTConvolver instances (below) */
@@ -353,8 +354,9 @@ int fftconv_crossfade_synchronize(fftconv_crossfade *h);
  *    therefore DEFINED as update(R'), R' = the response set the matrix holds
  *    with the listed pairs replaced: every output's overlap and pre_multiplied
  *    are zeroed as update does, and only the listed pairs are uploaded and
- *    transformed.  The sparse, lookahead and two-stage matrices offer the
- *    whole update only.
+ *    transformed.  The sparse matrix and the sparse crossfade have
+ *    update_pairs over their listed pairs; the lookahead and two-stage
+ *    matrices offer the whole update only.
  * Responses: pair p = o * inputs + i at responses + p * response_stride
  * (response_stride 0 = one response for every pair).  Supported blocks:
  * 32 <= next_power_of_two(max_block_size) <= 8192, else FFTCONV_E_UNSUPPORTED;
@@ -449,9 +451,10 @@ int fftconv_matrix_state(const fftconv_matrix *h, size_t out3[3]);
  * max_response_length is FFTCONV_E_INVALID; a block outside 32..8192
  * (next_power_of_two(max_block_size)) or indices past 32 bits is
  * FFTCONV_E_UNSUPPORTED; init returns NULL on error (fftconv_last_error).
- * Out of scope: a sparse crossfade and a sparse two-stage matrix (those take a
- * dense fftconv_matrix), changing the pattern after init, and any lookahead
- * for a sparse matrix (the dense one has fftconv_matrix_lookahead). */
+ * Crossfaded switching of a sparse matrix is fftconv_matrix_sparse_crossfade
+ * (below).  Out of scope: a sparse two-stage matrix (that takes a dense
+ * fftconv_matrix), changing the pattern after init, and any lookahead for a
+ * sparse matrix (the dense one has fftconv_matrix_lookahead). */
 fftconv_matrix_sparse *fftconv_matrix_sparse_init(int device, size_t inputs, size_t outputs, size_t pairs,
                                                   const uint32_t *pair_out, const uint32_t *pair_in,
                                                   const float *responses, size_t response_len,
@@ -464,6 +467,18 @@ int fftconv_matrix_sparse_update(fftconv_matrix_sparse *h, const float *response
                                  size_t response_stride);
 int fftconv_matrix_sparse_update_device(fftconv_matrix_sparse *h, const float *d_responses, size_t response_len,
                                         size_t response_stride, void *hip_stream);
+/* update(R') at the response_len of the last init / update, defined as
+ * fftconv_matrix_update_pairs is, with "pair" = a listed pair: the list is
+ * (pair_out[n], pair_in[n]), strictly ascending in (o, i), and every entry must
+ * belong to the pattern -- one that does not is FFTCONV_E_INVALID ("pair (o, i)
+ * is not in the pattern"), the handle unchanged.  Only the listed pairs are
+ * uploaded and transformed. */
+int fftconv_matrix_sparse_update_pairs(fftconv_matrix_sparse *h, size_t n_pairs, const uint32_t *pair_out,
+                                       const uint32_t *pair_in, const float *responses, size_t response_len,
+                                       size_t response_stride);
+int fftconv_matrix_sparse_update_pairs_device(fftconv_matrix_sparse *h, size_t n_pairs, const uint32_t *pair_out,
+                                              const uint32_t *pair_in, const float *d_responses, size_t response_len,
+                                              size_t response_stride, void *hip_stream);
 int fftconv_matrix_sparse_reset(fftconv_matrix_sparse *h); /* :296-306 */
 /* input [inputs][input_len], output [outputs][output_len], host memory;
  * input_len < output_len is FFTCONV_E_INVALID. */
@@ -692,6 +707,103 @@ int fftconv_matrix_crossfade_set_fused(fftconv_matrix_crossfade *h, int on);
 /* the path (0, 1 or 2 above) the next process() would take, a pending
  * response included */
 int fftconv_matrix_crossfade_path(const fftconv_matrix_crossfade *h);
+
+/* ---- SparseMatrixCrossfadeConvolver: crossfaded sparse matrix switching ----
+ * A sparse matrix crossfade has I inputs, O outputs and N >= 1 listed pairs,
+ * strictly ascending in (o, i).  It behaves as N reference
+ * CrossfadeConvolver<FFTConvolver> instances (src/crossfade_convolver.rs:3-105),
+ * one per listed pair, all created and updated together with the same lengths:
+ * instance n processes input i_n, output o is the sum of the instances listed
+ * for it; an output without pairs is 0.0 for every sample of every call, inside
+ * a fade too.  The crossfaders run in lockstep: one Crossfader, one pending
+ * response.  The device mixes the per-output sums, mix(sum a, sum b): equal to
+ * the definition within f32 rounding, not bitwise; in hold and Reached samples
+ * the mix returns a or b unchanged.  The pattern is fixed for the life of the
+ * handle.
+ * Everything fftconv_matrix_crossfade_* mirrors from the reference carries over
+ * word for word: new / init (init = new(sparse init(...), response_len,
+ * max_block_size, response_len)), update (idle: swap at once; fading: stored
+ * zero-padded and applied by the first process() after the fade), process
+ * advancing both convolvers by max_buffer_size, reset =
+ * FFTCONV_E_UNIMPLEMENTED, and the departures (non-finite samples are outside
+ * the contract; an update is an update of the whole set).  Row n of `responses`
+ * is pair n in list order; response_stride 0 = one response for all.  Errors are
+ * those of fftconv_matrix_sparse_init and fftconv_matrix_crossfade_*; no entry
+ * point allocates or waits on the host beyond what the dense crossfade's does.
+ * Paths (fftconv_matrix_sparse_crossfade_path): 0 composition (A and B as two
+ * plain sparse matrices, then the mix kernel), 1 fused with both convolvers
+ * live, 2 fused with one convolver idle -- chosen by the handle's state only,
+ * exactly as fftconv_matrix_crossfade chooses them ("in step" is its rule), and
+ * every path computes the same bits.  Every block size 32..8192 runs fused.
+ * Order of summation (part of the contract): per live convolver
+ * fftconv_matrix_sparse's, unchanged; then the mix as the dense crossfade
+ * applies it.  So (1) a fused call equals the composition call bit for bit;
+ * (2) output o is bit-identical, call by call through any script of updates and
+ * calls, to the single output of a dense fftconv_matrix_crossfade with k_o
+ * inputs that holds h[pair e], is fed x[i_e] and has the same
+ * max_response_length, max_buffer_size and crossfade_samples; (3) an output's
+ * bits depend only on its own pair list and the inputs it names: a pattern split
+ * by outputs over several handles gives identical rows; (4)
+ * process_device_steps equals the separate calls.
+ * update_pairs is update(R') bit for bit in outputs and in state: R', the base
+ * set, len', the merge rules during a fade, the one FFTCONV_E_UNSUPPORTED case
+ * and the bookkeeping of D are those of fftconv_matrix_crossfade_update_pairs
+ * with "pair" = a listed pair.  The list is (pair_out[n], pair_in[n]), strictly
+ * ascending in (o, i); every entry must belong to the pattern -- one that does
+ * not is FFTCONV_E_INVALID ("pair (o, i) is not in the pattern"), the handle
+ * unchanged.  diff_pairs and last_patch count listed pairs; a whole update
+ * gives {N, 0}. */
+fftconv_matrix_sparse_crossfade *fftconv_matrix_sparse_crossfade_init(int device, size_t inputs, size_t outputs,
+                                                                      size_t pairs, const uint32_t *pair_out,
+                                                                      const uint32_t *pair_in, const float *responses,
+                                                                      size_t response_len, size_t response_stride,
+                                                                      size_t max_block_size,
+                                                                      size_t max_response_length);
+/* `convolver` is cloned (the caller keeps ownership of its handle). */
+fftconv_matrix_sparse_crossfade *fftconv_matrix_sparse_crossfade_new(const fftconv_matrix_sparse *convolver,
+                                                                     size_t max_response_length,
+                                                                     size_t max_buffer_size,
+                                                                     size_t crossfade_samples);
+int fftconv_matrix_sparse_crossfade_update(fftconv_matrix_sparse_crossfade *h, const float *responses,
+                                           size_t response_len, size_t response_stride);
+int fftconv_matrix_sparse_crossfade_update_device(fftconv_matrix_sparse_crossfade *h, const float *d_responses,
+                                                  size_t response_len, size_t response_stride, void *hip_stream);
+int fftconv_matrix_sparse_crossfade_update_pairs(fftconv_matrix_sparse_crossfade *h, size_t n_pairs,
+                                                 const uint32_t *pair_out, const uint32_t *pair_in,
+                                                 const float *responses, size_t response_len,
+                                                 size_t response_stride);
+int fftconv_matrix_sparse_crossfade_update_pairs_device(fftconv_matrix_sparse_crossfade *h, size_t n_pairs,
+                                                        const uint32_t *pair_out, const uint32_t *pair_in,
+                                                        const float *d_responses, size_t response_len,
+                                                        size_t response_stride, void *hip_stream);
+/* |D|, in listed pairs */
+size_t fftconv_matrix_sparse_crossfade_diff_pairs(const fftconv_matrix_sparse_crossfade *h);
+/* the last applied swap: out2 = {pairs transformed, pairs copied}; a whole update gives {pairs, 0} */
+int fftconv_matrix_sparse_crossfade_last_patch(const fftconv_matrix_sparse_crossfade *h, size_t out2[2]);
+int fftconv_matrix_sparse_crossfade_reset(fftconv_matrix_sparse_crossfade *h);
+/* input [inputs][input_len], output [outputs][output_len], host memory. */
+int fftconv_matrix_sparse_crossfade_process(fftconv_matrix_sparse_crossfade *h, const float *input, size_t input_len,
+                                            float *output, size_t output_len);
+/* device memory, stream-ordered, as fftconv_matrix_crossfade_process_device */
+int fftconv_matrix_sparse_crossfade_process_device(fftconv_matrix_sparse_crossfade *h, const float *d_input,
+                                                   size_t in_stride, float *d_output, size_t out_stride,
+                                                   size_t output_len, void *hip_stream);
+/* `steps` consecutive process_device calls; the same bits as the separate calls. */
+int fftconv_matrix_sparse_crossfade_process_device_steps(fftconv_matrix_sparse_crossfade *h, const float *d_input,
+                                                         size_t in_stride, size_t in_step, float *d_output,
+                                                         size_t out_stride, size_t out_step, size_t output_len,
+                                                         size_t steps, void *hip_stream);
+int fftconv_matrix_sparse_crossfade_is_crossfading(const fftconv_matrix_sparse_crossfade *h); /* 1/0 */
+fftconv_matrix_sparse_crossfade *fftconv_matrix_sparse_crossfade_clone(const fftconv_matrix_sparse_crossfade *h);
+void fftconv_matrix_sparse_crossfade_destroy(fftconv_matrix_sparse_crossfade *h);
+int fftconv_matrix_sparse_crossfade_synchronize(fftconv_matrix_sparse_crossfade *h);
+size_t fftconv_matrix_sparse_crossfade_inputs(const fftconv_matrix_sparse_crossfade *h);
+size_t fftconv_matrix_sparse_crossfade_outputs(const fftconv_matrix_sparse_crossfade *h);
+size_t fftconv_matrix_sparse_crossfade_pairs(const fftconv_matrix_sparse_crossfade *h);
+/* on = 0: every call of this handle takes the composition path (default 1) */
+int fftconv_matrix_sparse_crossfade_set_fused(fftconv_matrix_sparse_crossfade *h, int on);
+/* the path (0, 1 or 2) the next process() would take, a pending response included */
+int fftconv_matrix_sparse_crossfade_path(const fftconv_matrix_sparse_crossfade *h);
 
 /* ---- MatrixTwoStageConvolver: two-stage partitioning for the matrix ----
  * A matrix two-stage convolver (inputs I, outputs O, head block max_block_size,
