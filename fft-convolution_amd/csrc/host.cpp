@@ -2752,6 +2752,224 @@ struct SparseMatrixCore {
 };
 
 // ---------------------------------------------------------------------------
+// SparseMatrixLookaheadCore -- the SparseMatrixCore's N instances with one
+// level of far-row windows (matrix_sp_la.hip).  The sparse core `m`
+// owns the geometry, the pattern, H, the delay lines, the stream, the IR
+// transforms and {current, active, fill}, as MatrixLookaheadCore's dense core
+// does; this core adds the near / far partial sums, its own plan (per output
+// the near and far part counts over its pair list, the far workgroups ordered
+// by anchor class) and the block count {t, tv} that schedules the anchors.
+// (m.part, m.plan and m.wg are the plain sparse walk's and unused here.)
+// ---------------------------------------------------------------------------
+struct SparseMatrixLookaheadCore {
+    static constexpr size_t Q = kMatrixLaQ;
+    SparseMatrixCore m;
+    DevPtr<float2> npart;  // [sum Pn_o][B] at active = S
+    DevPtr<float2> far;    // [sum Pf_o][Q][B] at active = S
+    DevPtr<int> nplan, fplan, d_coff;
+    DevPtr<int4> nwg, fwg;
+    size_t PnT = 0, PfT = 0;   // for the current active
+    int coff[Q + 1] = {};      // the host's copy of the class offsets, from its copy of rowptr
+    int class_outputs[Q] = {}; // outputs with at least one pair, per anchor class
+    long long t = 0, tv = 0;
+    bool windows = true;
+
+    int near_parts(size_t o) const { return matrix_sp_la_pn((long long)m.pairs_of(o), (int)m.act); }
+    int far_parts(size_t o) const { return matrix_sp_la_pf((long long)m.pairs_of(o), (int)m.act); }
+    // outputs with at least one pair that anchor when the next block starts
+    int anchors() const {
+        if (!windows || m.act <= Q || m.cur >= m.act) return 0;
+        return class_outputs[(size_t)(t % (long long)Q)];
+    }
+    void invalidate() { tv = m.fill ? t + 1 : t; }
+
+    // the sums the plan kernel computes, from the host's copy of the pattern
+    void count(size_t active, size_t *pn, size_t *pf, int *offsets) const {
+        size_t n = 0, cls[Q] = {};
+        for (size_t o = 0; o < m.O; ++o) {
+            n += (size_t)matrix_sp_la_pn((long long)m.pairs_of(o), (int)active);
+            cls[o % Q] += (size_t)matrix_sp_la_pf((long long)m.pairs_of(o), (int)active);
+        }
+        size_t f = 0;
+        for (size_t c = 0; c < Q; ++c) {
+            if (offsets) offsets[c] = (int)f;
+            f += cls[c];
+        }
+        if (offsets) offsets[Q] = (int)f;
+        *pn = n;
+        *pf = f;
+    }
+    // the device plan for the current active, behind the stream's earlier work
+    int rebuild_plan(hipStream_t s) {
+        count(m.act, &PnT, &PfT, coff);
+        HIP_TRY(launch_matrix_sp_la_plan(m.d_rowptr.p, nplan.p, fplan.p, nwg.p, fwg.p, d_coff.p, (int)m.O, (int)m.act, s));
+        return FFTCONV_OK;
+    }
+
+    int alloc_extra() {
+        size_t pn = 0, pf = 0;
+        count(m.S, &pn, &pf, nullptr);  // (every count is largest at active = S)
+        if (m.I + pn + pf > (size_t)INT32_MAX || 2 * pf > (size_t)INT32_MAX)
+            return fail(FFTCONV_E_UNSUPPORTED, "geometry exceeds 32-bit indexing");
+        if (int r = npart.alloc(pn * m.B)) return r;
+        if (int r = far.alloc(pf * Q * m.B)) return r;
+        if (int r = nplan.alloc(m.O + 1)) return r;
+        if (int r = fplan.alloc(m.O + 1)) return r;
+        if (int r = d_coff.alloc(Q + 1)) return r;
+        if (int r = nwg.alloc(pn)) return r;
+        if (int r = fwg.alloc(2 * pf)) return r;
+        for (size_t c = 0; c < Q; ++c) class_outputs[c] = 0;
+        for (size_t o = 0; o < m.O; ++o)
+            if (m.pairs_of(o)) ++class_outputs[o % Q];
+        return FFTCONV_OK;
+    }
+
+    int init(int dev, size_t inputs, size_t outputs, size_t pairs, const uint32_t *po, const uint32_t *pi,
+             const float *responses, size_t len, size_t stride, size_t max_block, size_t max_len) {
+        if (int r = SparseMatrixCore::check_pattern(inputs, outputs, pairs, po, pi)) return r;
+        if (max_len >= len && next_pow2(max_block) > ((size_t)1 << kMatrixLaMaxLog2B))
+            return fail(FFTCONV_E_UNSUPPORTED, "sparse matrix lookahead block size " + std::to_string(next_pow2(max_block)) +
+                                                   " outside 32..512 (use the SparseMatrixConvolver)");
+        if (int r = m.init(dev, inputs, outputs, pairs, po, pi, responses, len, stride, max_block, max_len)) return r;
+        DeviceGuard g(dev);
+        t = tv = 0;
+        if (int r = alloc_extra()) return r;
+        if (int r = rebuild_plan(m.stream)) return r;
+        HIP_TRY(hipStreamSynchronize(m.stream));
+        return FFTCONV_OK;
+    }
+    int update_device(const float *src, size_t stride, size_t len, hipStream_t s) {
+        if (int r = m.update_device(src, stride, len, s)) return r;
+        if (m.ir_len == 0) return FFTCONV_OK;
+        if (int r = rebuild_plan(s)) return r;
+        invalidate();
+        return FFTCONV_OK;
+    }
+    int update_host(const float *src, size_t len, size_t stride) {
+        if (int r = m.update_host(src, len, stride)) return r;
+        if (m.ir_len == 0) return FFTCONV_OK;
+        DeviceGuard g(m.device);
+        if (int r = rebuild_plan(m.stream)) return r;
+        invalidate();
+        return FFTCONV_OK;
+    }
+    // update(R') of the sparse core at the held length: active and the plan stay;
+    // every window is dropped, the untouched outputs' too
+    int update_pairs(size_t n, const uint32_t *pair_out, const uint32_t *pair_in, const float *src, bool d_src,
+                     size_t len, size_t stride, hipStream_t s) {
+        if (int r = m.update_pairs(n, pair_out, pair_in, src, d_src, len, stride, s)) return r;
+        invalidate();
+        return FFTCONV_OK;
+    }
+    int reset(hipStream_t s) {
+        if (m.fill) ++t;  // (the block in progress is dropped: its number is not used again)
+        if (int r = m.zero_state(s)) return r;
+        invalidate();
+        return FFTCONV_OK;
+    }
+
+    int process_device(const float *din, size_t is, float *dout, size_t os, size_t n, hipStream_t s) {
+        if (n > (size_t)INT32_MAX) return fail(FFTCONV_E_UNSUPPORTED, "process length exceeds 2^31-1");
+        if (n == 0) return FFTCONV_OK;
+        if (m.act == 0) {  // :216-219 -- zero output, state untouched
+            HIP_TRY(hipMemset2DAsync(dout, os * sizeof(float), 0, n * sizeof(float), m.O, s));
+            return FFTCONV_OK;
+        }
+        MatrixSpLaArgs la{};
+        MatrixArgs &a = la.m;
+        a.H = m.H.p; a.X = m.X.p; a.ovl = m.ovl.p; a.ib = m.ib.p; a.pre = m.pre.p; a.part = npart.p; a.tw = m.tw.p;
+        a.in_stride = (long long)is;
+        a.out_stride = (long long)os;
+        a.I = (int)m.I; a.O = (int)m.O; a.S = (int)m.S;
+        a.act = (int)m.act;
+        // by the whole H, as the dense lookahead matrix
+        a.nt_h = Variant::current().nt_matrix(m.H.bytes()) ? 1 : 0;
+        la.rowptr = m.d_rowptr.p; la.col = m.d_col.p;
+        la.nplan = nplan.p; la.fplan = fplan.p; la.nwg = nwg.p; la.fwg = fwg.p;
+        la.far = far.p;
+        la.N = (int)m.N;
+        la.PnT = (int)PnT;
+        la.PfT = (int)PfT;
+        size_t processed = 0;
+        while (processed < n) {                                     // :222-294
+            const size_t k = std::min(n - processed, m.B - m.fill); // :224-227
+            if (m.fill == 0 && (!windows || m.cur >= m.act)) tv = t + 1;  // no anchor in this block
+            a.in = din + processed;
+            a.out = dout + processed;
+            a.cur = (int)m.cur;
+            a.fill = (int)m.fill;
+            a.k = (int)k;
+            la.t = t;
+            la.tv = tv;
+            if (matrix_la_steady(t, tv)) {  // the anchoring class only
+                const size_t c = (size_t)(t % (long long)Q);
+                la.fbase = coff[c];
+                la.flen = coff[c + 1] - coff[c];
+            } else {
+                la.fbase = 0;
+                la.flen = (int)PfT;
+            }
+            HIP_TRY(launch_matrix_sp_la_chunk(m.log2b, la, s));
+            m.fill += k;
+            if (m.fill == m.B) {                                    // :277-291
+                m.fill = 0;
+                m.cur = m.cur > 0 ? m.cur - 1 : m.act - 1;
+                ++t;
+            }
+            processed += k;
+        }
+        return FFTCONV_OK;
+    }
+
+    int process_device_steps(const float *din, size_t is, size_t in_step, float *dout, size_t os, size_t out_step,
+                             size_t n, size_t steps, hipStream_t s) {
+        for (size_t k = 0; k < steps; ++k)
+            if (int r = process_device(din + k * in_step, is, dout + k * out_step, os, n, s)) return r;
+        return FFTCONV_OK;
+    }
+
+    int process_host(const float *in, size_t in_len, float *out, size_t out_len) {
+        if (in_len < out_len) return fail(FFTCONV_E_INVALID, "input slice shorter than output (range end index out of range)");
+        if (out_len == 0) return FFTCONV_OK;
+        DeviceGuard g(m.device);
+        if (int r = m.order.enter(m.stream)) return r;
+        if (int r = m.scratch.ensure(m.I * out_len, m.O * out_len)) return r;
+        HIP_TRY(hipMemcpy2DAsync(m.scratch.in.p, out_len * sizeof(float), in, in_len * sizeof(float),
+                                 out_len * sizeof(float), m.I, hipMemcpyHostToDevice, m.stream));
+        if (int r = process_device(m.scratch.in.p, out_len, m.scratch.out.p, out_len, out_len, m.stream)) return r;
+        HIP_TRY(hipMemcpyAsync(out, m.scratch.out.p, m.O * out_len * sizeof(float), hipMemcpyDeviceToHost, m.stream));
+        HIP_TRY(hipStreamSynchronize(m.stream));
+        return FFTCONV_OK;
+    }
+
+    int clone_from(const SparseMatrixLookaheadCore &o) {  // #[derive(Clone)]: the windows, the plans and {t, tv} too
+        if (int r = m.clone_from(o.m)) return r;
+        DeviceGuard g(m.device);
+        t = o.t;
+        tv = o.tv;
+        windows = o.windows;
+        PnT = o.PnT;
+        PfT = o.PfT;
+        std::copy(o.coff, o.coff + Q + 1, coff);
+        std::copy(o.class_outputs, o.class_outputs + Q, class_outputs);
+        auto cp = [&](auto &dst, const auto &src) -> int {
+            if (int r = dst.alloc(src.n)) return r;
+            if (src.n) HIP_TRY(hipMemcpyAsync(dst.p, src.p, src.bytes(), hipMemcpyDeviceToDevice, m.stream));
+            return FFTCONV_OK;
+        };
+        if (int r = cp(far, o.far)) return r;
+        if (int r = cp(nplan, o.nplan)) return r;
+        if (int r = cp(fplan, o.fplan)) return r;
+        if (int r = cp(d_coff, o.d_coff)) return r;
+        if (int r = cp(nwg, o.nwg)) return r;
+        if (int r = cp(fwg, o.fwg)) return r;
+        if (int r = npart.alloc(o.npart.n)) return r;  // (rewritten by every block before it is read)
+        HIP_TRY(hipStreamSynchronize(m.stream));
+        return FFTCONV_OK;
+    }
+};
+
+// ---------------------------------------------------------------------------
 // MatrixCrossfadeCore -- I x O CrossfadeConvolver<FFTConvolver> instances
 // (o, i) in lockstep: two MatrixCores A and B on the handle's
 // stream, ONE Crossfader and one response_pending for all of them, the mix
@@ -4146,6 +4364,7 @@ struct fftconv_crossfade { CrossfadeCore core; };
 struct fftconv_matrix { MatrixCore core; };
 struct fftconv_matrix_sparse { SparseMatrixCore core; };
 struct fftconv_matrix_lookahead { MatrixLookaheadCore core; };
+struct fftconv_matrix_sparse_lookahead { SparseMatrixLookaheadCore core; };
 struct fftconv_matrix_crossfade { MatrixCrossfadeCore core; };
 struct fftconv_matrix_sparse_crossfade { SparseMatrixCrossfadeCore core; };
 struct fftconv_matrix_twostage { MatrixTwoStageCore core; };
@@ -4761,6 +4980,121 @@ int fftconv_matrix_sparse_state(const fftconv_matrix_sparse *h, size_t out3[3]) 
     if (!h) return fail(FFTCONV_E_INVALID, "null handle");
     out3[0] = h->core.cur; out3[1] = h->core.act; out3[2] = h->core.fill;
     return FFTCONV_OK;
+}
+
+// ---- sparse matrix with far-row windows ---------------------------
+fftconv_matrix_sparse_lookahead *fftconv_matrix_sparse_lookahead_init(int device, size_t inputs, size_t outputs,
+                                                                      size_t pairs, const uint32_t *pair_out,
+                                                                      const uint32_t *pair_in, const float *responses,
+                                                                      size_t response_len, size_t response_stride,
+                                                                      size_t max_block_size,
+                                                                      size_t max_response_length) {
+    set_error("");
+    auto *h = new (std::nothrow) fftconv_matrix_sparse_lookahead();
+    if (!h) { set_error("out of host memory"); return nullptr; }
+    int r = h->core.init(device, inputs, outputs, pairs, pair_out, pair_in, responses, response_len, response_stride,
+                         max_block_size, max_response_length);
+    return make_or_null(r, h);
+}
+int fftconv_matrix_sparse_lookahead_update(fftconv_matrix_sparse_lookahead *h, const float *responses,
+                                           size_t response_len, size_t response_stride) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.update_host(responses, response_len, response_stride);
+}
+int fftconv_matrix_sparse_lookahead_update_device(fftconv_matrix_sparse_lookahead *h, const float *d_responses,
+                                                  size_t response_len, size_t response_stride, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.m.device);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int r = h->core.m.order.enter(s)) return r;
+    return h->core.update_device(d_responses, response_stride, response_len, s);
+}
+int fftconv_matrix_sparse_lookahead_update_pairs(fftconv_matrix_sparse_lookahead *h, size_t n_pairs,
+                                                 const uint32_t *pair_out, const uint32_t *pair_in,
+                                                 const float *responses, size_t response_len, size_t response_stride) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.update_pairs(n_pairs, pair_out, pair_in, responses, false, response_len, response_stride,
+                                h->core.m.stream);
+}
+int fftconv_matrix_sparse_lookahead_update_pairs_device(fftconv_matrix_sparse_lookahead *h, size_t n_pairs,
+                                                        const uint32_t *pair_out, const uint32_t *pair_in,
+                                                        const float *d_responses, size_t response_len,
+                                                        size_t response_stride, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.update_pairs(n_pairs, pair_out, pair_in, d_responses, true, response_len, response_stride,
+                                (hipStream_t)hip_stream);
+}
+int fftconv_matrix_sparse_lookahead_reset(fftconv_matrix_sparse_lookahead *h) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.m.device);
+    if (int r = h->core.m.order.enter(h->core.m.stream)) return r;
+    if (int r = h->core.reset(h->core.m.stream)) return r;
+    HIP_TRY(hipStreamSynchronize(h->core.m.stream));
+    return FFTCONV_OK;
+}
+int fftconv_matrix_sparse_lookahead_process(fftconv_matrix_sparse_lookahead *h, const float *input, size_t input_len,
+                                            float *output, size_t output_len) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.process_host(input, input_len, output, output_len);
+}
+int fftconv_matrix_sparse_lookahead_process_device(fftconv_matrix_sparse_lookahead *h, const float *d_input,
+                                                   size_t in_stride, float *d_output, size_t out_stride, size_t len,
+                                                   void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.m.device);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int r = h->core.m.order.enter(s)) return r;
+    return h->core.process_device(d_input, in_stride, d_output, out_stride, len, s);
+}
+int fftconv_matrix_sparse_lookahead_process_device_steps(fftconv_matrix_sparse_lookahead *h, const float *d_input,
+                                                         size_t in_stride, size_t in_step, float *d_output,
+                                                         size_t out_stride, size_t out_step, size_t len, size_t steps,
+                                                         void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.m.device);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int r = h->core.m.order.enter(s)) return r;
+    return h->core.process_device_steps(d_input, in_stride, in_step, d_output, out_stride, out_step, len, steps, s);
+}
+fftconv_matrix_sparse_lookahead *fftconv_matrix_sparse_lookahead_clone(const fftconv_matrix_sparse_lookahead *h) {
+    if (!h) { set_error("null handle"); return nullptr; }
+    auto *c = new (std::nothrow) fftconv_matrix_sparse_lookahead();
+    if (!c) { set_error("out of host memory"); return nullptr; }
+    return make_or_null(c->core.clone_from(h->core), c);
+}
+void fftconv_matrix_sparse_lookahead_destroy(fftconv_matrix_sparse_lookahead *h) { delete h; }
+int fftconv_matrix_sparse_lookahead_synchronize(fftconv_matrix_sparse_lookahead *h) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    DeviceGuard g(h->core.m.device);
+    return h->core.m.order.drain(h->core.m.stream);
+}
+size_t fftconv_matrix_sparse_lookahead_inputs(const fftconv_matrix_sparse_lookahead *h) { return h ? h->core.m.I : 0; }
+size_t fftconv_matrix_sparse_lookahead_outputs(const fftconv_matrix_sparse_lookahead *h) { return h ? h->core.m.O : 0; }
+size_t fftconv_matrix_sparse_lookahead_pairs(const fftconv_matrix_sparse_lookahead *h) { return h ? h->core.m.N : 0; }
+size_t fftconv_matrix_sparse_lookahead_block_size(const fftconv_matrix_sparse_lookahead *h) {
+    return h ? h->core.m.B : 0;
+}
+size_t fftconv_matrix_sparse_lookahead_seg_count(const fftconv_matrix_sparse_lookahead *h) {
+    return h ? h->core.m.S : 0;
+}
+int fftconv_matrix_sparse_lookahead_state(const fftconv_matrix_sparse_lookahead *h, size_t out3[3]) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    out3[0] = h->core.m.cur; out3[1] = h->core.m.act; out3[2] = h->core.m.fill;
+    return FFTCONV_OK;
+}
+int fftconv_matrix_sparse_lookahead_near_parts(const fftconv_matrix_sparse_lookahead *h, size_t output) {
+    return h && output < h->core.m.O ? h->core.near_parts(output) : 0;
+}
+int fftconv_matrix_sparse_lookahead_far_parts(const fftconv_matrix_sparse_lookahead *h, size_t output) {
+    return h && output < h->core.m.O ? h->core.far_parts(output) : 0;
+}
+int fftconv_matrix_sparse_lookahead_set_windows(fftconv_matrix_sparse_lookahead *h, int on) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    h->core.windows = on != 0;
+    return FFTCONV_OK;
+}
+int fftconv_matrix_sparse_lookahead_anchors(const fftconv_matrix_sparse_lookahead *h) {
+    return h ? h->core.anchors() : 0;
 }
 
 // ---- matrix crossfade ---------------------------------------------

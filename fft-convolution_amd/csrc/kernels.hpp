@@ -472,6 +472,42 @@ __host__ __device__ inline int matrix_la_far_outputs(long long t, long long tv, 
 // the chunk's two launches (32 <= B <= 512)
 hipError_t launch_matrix_la_chunk(int log2b, const MatrixLaArgs &a, hipStream_t s);
 
+// SparseMatrixLookaheadConvolver (matrix_sp_la.hip): one chunk of a
+// sparse matrix (MatrixSpArgs' H = [N][S][B], rowptr, col) with MatrixLaArgs'
+// far-row windows, every output with its own part counts over its pair list:
+//   Pn_o = matrix_la_parts(k_o * (min(Q, act) - 1))
+//   Pf_o = matrix_la_parts(k_o * (act - Q)), 0 when act <= Q or k_o == 0
+// m.part = [sum Pn_o][B] (output o's near parts at nplan[o]); m.P and m.rpp are
+// unused.  The window rows of output o start at far row fplan[o].
+struct MatrixSpLaArgs {
+    MatrixArgs m;
+    const int *rowptr;     // [O + 1] pairs of output o = [rowptr[o], rowptr[o + 1])
+    const int *col;        // [N] input of pair n
+    const int *nplan;      // [O + 1] prefix sums of Pn_o
+    const int *fplan;      // [O + 1] prefix sums of Pf_o, in output order
+    const int4 *nwg;       // [PnT] near workgroup m = nplan[o] + p: {rowptr[o], k_o, p, Pn_o}
+    const int4 *fwg;       // [2 * PfT] far workgroups ordered by (o % Q, o, p), two entries each:
+                           // {rowptr[o], k_o, o, p}, {Pf_o, fplan[o] + p, 0, 0}
+    float2 *far;           // [PfT][Q][B] far partial sums, window row = block % Q
+    int N;                 // pairs
+    int PnT, PfT;          // nplan[O], fplan[O]
+    int fbase, flen;       // the far workgroups of this launch: descriptors [fbase, fbase + flen)
+    long long t, tv;       // as MatrixLaArgs
+};
+__host__ __device__ inline int matrix_sp_la_pn(long long ko, int act) {
+    const int nm = act < kMatrixLaQ ? act : kMatrixLaQ;
+    return matrix_la_parts(ko * (nm > 0 ? nm - 1 : 0));
+}
+__host__ __device__ inline int matrix_sp_la_pf(long long ko, int act) {
+    return act > kMatrixLaQ && ko > 0 ? matrix_la_parts(ko * (act - kMatrixLaQ)) : 0;
+}
+// nplan, fplan, nwg, fwg and coff[0..Q] (the class offsets into fwg's pairs of
+// entries) for `act` active segments, one workgroup on s
+hipError_t launch_matrix_sp_la_plan(const int *rowptr, int *nplan, int *fplan, int4 *nwg, int4 *fwg, int *coff, int O,
+                                    int act, hipStream_t s);
+// the chunk's two launches (32 <= B <= 512)
+hipError_t launch_matrix_sp_la_chunk(int log2b, const MatrixSpLaArgs &a, hipStream_t s);
+
 // MatrixCrossfadeConvolver (matrix_xf.hip): one chunk of the two
 // matrices A and B of a crossfaded handle while they are in step (equal
 // {current, active, fill} at every call since creation, so X[0] and X[1], ib[0]

@@ -160,6 +160,28 @@ SIGNATURES = {
     "fftconv_matrix_sparse_seg_count": (_sz, [_vp]),
     "fftconv_matrix_sparse_output_parts": (_i, [_vp, _sz]),
     "fftconv_matrix_sparse_state": (_i, [_vp, C.POINTER(_sz)]),
+    "fftconv_matrix_sparse_lookahead_init": (_vp, [_i, _sz, _sz, _sz, _u32p, _u32p, _fp, _sz, _sz, _sz, _sz]),
+    "fftconv_matrix_sparse_lookahead_update": (_i, [_vp, _fp, _sz, _sz]),
+    "fftconv_matrix_sparse_lookahead_update_device": (_i, [_vp, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_sparse_lookahead_update_pairs": (_i, [_vp, _sz, _u32p, _u32p, _fp, _sz, _sz]),
+    "fftconv_matrix_sparse_lookahead_update_pairs_device": (_i, [_vp, _sz, _u32p, _u32p, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_sparse_lookahead_reset": (_i, [_vp]),
+    "fftconv_matrix_sparse_lookahead_process": (_i, [_vp, _fp, _sz, _fp, _sz]),
+    "fftconv_matrix_sparse_lookahead_process_device": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_sparse_lookahead_process_device_steps": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _sz, _sz, _vp]),
+    "fftconv_matrix_sparse_lookahead_clone": (_vp, [_vp]),
+    "fftconv_matrix_sparse_lookahead_destroy": (None, [_vp]),
+    "fftconv_matrix_sparse_lookahead_synchronize": (_i, [_vp]),
+    "fftconv_matrix_sparse_lookahead_inputs": (_sz, [_vp]),
+    "fftconv_matrix_sparse_lookahead_outputs": (_sz, [_vp]),
+    "fftconv_matrix_sparse_lookahead_pairs": (_sz, [_vp]),
+    "fftconv_matrix_sparse_lookahead_block_size": (_sz, [_vp]),
+    "fftconv_matrix_sparse_lookahead_seg_count": (_sz, [_vp]),
+    "fftconv_matrix_sparse_lookahead_state": (_i, [_vp, C.POINTER(_sz)]),
+    "fftconv_matrix_sparse_lookahead_near_parts": (_i, [_vp, _sz]),
+    "fftconv_matrix_sparse_lookahead_far_parts": (_i, [_vp, _sz]),
+    "fftconv_matrix_sparse_lookahead_set_windows": (_i, [_vp, _i]),
+    "fftconv_matrix_sparse_lookahead_anchors": (_i, [_vp]),
     "fftconv_matrix_crossfade_init": (_vp, [_i, _sz, _sz, _fp, _sz, _sz, _sz, _sz]),
     "fftconv_matrix_crossfade_new": (_vp, [_vp, _sz, _sz, _sz]),
     "fftconv_matrix_crossfade_update": (_i, [_vp, _fp, _sz, _sz]),
@@ -894,6 +916,103 @@ class SparseMatrixConvolver(_UpdatePairs, _Base):
         return tuple(int(v) for v in out)
 
 
+class SparseMatrixLookaheadConvolver(_UpdatePairs, _Base):
+    """The SparseMatrixConvolver with the MatrixLookaheadConvolver's far-row
+    windows (fftconv.h, "SparseMatrixLookaheadConvolver"): one FFTConvolver
+    instance per listed (output, input) pair, an output's rows s >= period summed
+    once every `period` blocks for the next `period` blocks.  Blocks 32..512."""
+
+    _prefix = "matrix_sparse_lookahead"
+
+    def __init__(self, h, inputs: int, outputs: int, pairs: int, pair_list=None):
+        super().__init__(h, inputs)
+        self.inputs = inputs
+        self.outputs = outputs
+        self.pairs = pairs
+        self._pair_list = [(int(o), int(i)) for o, i in pair_list] if pair_list is not None else None
+
+    @classmethod
+    def init(cls, pairs, responses, inputs: int, outputs: int, max_block_size: int, max_response_length: int,
+             device: int = 0):
+        """pairs: (output, input) tuples, strictly ascending; responses[n] is
+        the response of pairs[n]."""
+        po, pi = _pair_arrays(pairs)
+        r = _f32(responses)
+        if r.ndim != 2 or r.shape[0] != len(po):
+            raise ValueError("responses must be [pairs][len]")
+        n = r.shape[1]
+        h = lib().fftconv_matrix_sparse_lookahead_init(device, inputs, outputs, len(po), po.ctypes.data_as(_u32p),
+                                                       pi.ctypes.data_as(_u32p), _p(r), n, n, max_block_size,
+                                                       max_response_length)
+        return cls(_handle(h), inputs, outputs, len(po), list(zip(po.tolist(), pi.tolist())))
+
+    def update(self, responses):
+        """update() of every listed pair with responses[pairs][len]."""
+        r = _f32(responses)
+        if r.ndim != 2 or r.shape[0] != self.pairs:
+            raise ValueError("responses must be [pairs][len]")
+        _check(self._fn("update")(self._h, _p(r), r.shape[1], r.shape[1]))
+
+    def update_device(self, d_responses: int, response_len: int, stride: int = 0, stream: int = 0):
+        """update() from device memory (pair n, in list order, at d_responses +
+        4 * n * stride; stride 0 = one response for every pair), stream-ordered."""
+        _check(self._fn("update_device")(self._h, C.c_void_p(d_responses), response_len, stride,
+                                         C.c_void_p(stream) if stream else None))
+
+    def reset(self):
+        _check(self._fn("reset")(self._h))
+
+    def process(self, inp, out_len: int | None = None) -> np.ndarray:
+        """x[inputs][n] -> y[outputs][out_len or n]."""
+        x = _f32(inp)
+        if x.ndim != 2 or x.shape[0] != self.inputs:
+            raise ValueError(f"input must be [{self.inputs}][n]")
+        n_in = x.shape[1]
+        n = n_in if out_len is None else out_len
+        y = np.zeros((self.outputs, n), np.float32)
+        _check(self._fn("process")(self._h, _p(x), n_in, _p(y), n))
+        return y
+
+    def clone(self):
+        return SparseMatrixLookaheadConvolver(_handle(self._fn("clone")(self._h)), self.inputs, self.outputs,
+                                              self.pairs, self._pair_list)
+
+    @property
+    def block_size(self) -> int:
+        return int(self._fn("block_size")(self._h))
+
+    @property
+    def seg_count(self) -> int:
+        return int(self._fn("seg_count")(self._h))
+
+    @staticmethod
+    def period() -> int:
+        """Q, the MatrixLookaheadConvolver's."""
+        return int(lib().fftconv_matrix_lookahead_period())
+
+    def near_parts(self, o: int) -> int:
+        """Pn_o: workgroups sharing output o's near sum, for the current active_seg_count."""
+        return int(self._fn("near_parts")(self._h, o))
+
+    def far_parts(self, o: int) -> int:
+        """Pf_o: workgroups sharing output o's far sum (0: no far rows or no pairs)."""
+        return int(self._fn("far_parts")(self._h, o))
+
+    def set_windows(self, on: bool):
+        """off: every output sums its far rows in full on every block (the same bits)."""
+        _check(self._fn("set_windows")(self._h, 1 if on else 0))
+
+    def anchors(self) -> int:
+        """Outputs with at least one pair that anchor when the next block starts."""
+        return int(self._fn("anchors")(self._h))
+
+    def state(self):
+        """(current, active_seg_count, input_buffer_fill) of the whole matrix."""
+        out = (C.c_size_t * 3)()
+        _check(self._fn("state")(self._h, out))
+        return tuple(int(v) for v in out)
+
+
 class MatrixCrossfadeConvolver(_UpdatePairs, _Base):
     """Crossfaded response switching for the matrix (fftconv.h,
     "MatrixCrossfadeConvolver"): inputs x outputs CrossfadeConvolver<FFTConvolver>
@@ -1155,7 +1274,8 @@ class MatrixTwoStageConvolver(_Base):
 
 __all__ = [
     "Fft", "FFTConvolver", "TwoStageFFTConvolver", "CrossfadeConvolver", "MatrixConvolver",
-    "MatrixLookaheadConvolver", "SparseMatrixConvolver", "MatrixCrossfadeConvolver", "MatrixTwoStageConvolver",
+    "MatrixLookaheadConvolver", "SparseMatrixConvolver", "SparseMatrixLookaheadConvolver",
+    "MatrixCrossfadeConvolver", "SparseMatrixCrossfadeConvolver", "MatrixTwoStageConvolver",
     "ConvolutionPanic",
     "NotImplementedInReference", "DeviceError", "complex_size", "compute_tail_block_size", "device_count",
     "lib", "LIB_PATH", "SIGNATURES",

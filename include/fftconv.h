@@ -65,6 +65,7 @@ typedef struct fftconv_matrix fftconv_matrix;       /* inputs x outputs FFTConvo
 typedef struct fftconv_matrix_sparse fftconv_matrix_sparse; /* one FFTConvolver instance per listed (output, input) pair (below) */
 typedef struct fftconv_matrix_sparse_crossfade fftconv_matrix_sparse_crossfade; /* one CrossfadeConvolver per listed pair (below) */
 typedef struct fftconv_matrix_lookahead fftconv_matrix_lookahead; /* the matrix with far-row windows (below) */
+typedef struct fftconv_matrix_sparse_lookahead fftconv_matrix_sparse_lookahead; /* the sparse matrix with far-row windows (below) */
 typedef struct fftconv_matrix_crossfade fftconv_matrix_crossfade; /* inputs x outputs CrossfadeConvolver<FFTConvolver> instances (below) */
 typedef struct fftconv_matrix_twostage fftconv_matrix_twostage;   /* inputs x outputs TwoStageFFTConvolver instances (below) */
 
@@ -452,9 +453,10 @@ int fftconv_matrix_state(const fftconv_matrix *h, size_t out3[3]);
  * (next_power_of_two(max_block_size)) or indices past 32 bits is
  * FFTCONV_E_UNSUPPORTED; init returns NULL on error (fftconv_last_error).
  * Crossfaded switching of a sparse matrix is fftconv_matrix_sparse_crossfade
- * (below).  Out of scope: a sparse two-stage matrix (that takes a dense
- * fftconv_matrix), changing the pattern after init, and any lookahead for a
- * sparse matrix (the dense one has fftconv_matrix_lookahead). */
+ * (below); far-row windows for a sparse matrix with long responses and small
+ * blocks are the fftconv_matrix_sparse_lookahead handle, below.  Out of scope: a sparse
+ * two-stage matrix (that takes a dense fftconv_matrix) and changing the pattern
+ * after init. */
 fftconv_matrix_sparse *fftconv_matrix_sparse_init(int device, size_t inputs, size_t outputs, size_t pairs,
                                                   const uint32_t *pair_out, const uint32_t *pair_in,
                                                   const float *responses, size_t response_len,
@@ -545,7 +547,8 @@ int fftconv_matrix_sparse_state(const fftconv_matrix_sparse *h, size_t out3[3]);
  * FFTCONV_E_UNSUPPORTED (use fftconv_matrix there); other errors as
  * fftconv_matrix_init.  Everything is reserved at init: update allocates
  * nothing and does not wait on the host.
- * The crossfaded, two-stage and sparse matrices stay without lookahead. */
+ * The sparse matrix has the same windows as the fftconv_matrix_sparse_lookahead
+ * handle, below; the crossfaded and two-stage matrices stay without lookahead. */
 fftconv_matrix_lookahead *fftconv_matrix_lookahead_init(int device, size_t inputs, size_t outputs,
                                                         const float *responses, size_t response_len,
                                                         size_t response_stride, size_t max_block_size,
@@ -583,6 +586,95 @@ int fftconv_matrix_lookahead_set_windows(fftconv_matrix_lookahead *h, int on);
 /* outputs that anchor when the next block starts (0 while windows are off,
  * active <= Q or current >= active) */
 int fftconv_matrix_lookahead_anchors(const fftconv_matrix_lookahead *h);
+
+/* ---- SparseMatrixLookaheadConvolver: far-row windows for the sparse matrix ----
+ * Definition: exactly fftconv_matrix_sparse's -- I inputs, O outputs, N >= 1
+ * pairs strictly ascending in (o, i), N FFTConvolver instances in lockstep, one
+ * per listed pair; an output without pairs is 0.0, an input nobody reads is
+ * accepted; one {current, active_seg_count, input_buffer_fill}; the pattern is
+ * fixed for the life of the handle; the dense matrix's departures carry over.
+ * What differs is the schedule of the spectral sum, which is
+ * fftconv_matrix_lookahead's with the same period Q =
+ * fftconv_matrix_lookahead_period(): output o anchors on the blocks t = o
+ * (mod Q), one walk over its far rows produces the far sums of blocks t .. t +
+ * Q - 1; after init, reset, update, update_pairs and while current >= active
+ * an output sums its far rows in full until its next anchor.  update_pairs
+ * drops the windows of every output, the untouched ones' too.
+ * Order of summation (part of the contract): fftconv_matrix_lookahead's with
+ * output o's pair list (k_o entries, entry e = the e-th pair listed for o, i_e
+ * its input) in place of 0..I-1: pre[o] = near[o] + far[o], then the row-0
+ * terms X[i_e][current] (.) H[pair e][0] in ascending e.
+ *  - near[o]: the rows (e, s), 1 <= s < min(Q, active), flattened pair-major,
+ *    in Pn_o parts (fftconv_matrix_sparse_lookahead_near_parts: the rule of
+ *    fftconv_matrix_lookahead_near_parts on k_o * (min(Q, active) - 1) rows);
+ *    groups and the order inside a part as fftconv_matrix_lookahead's near sum.
+ *  - far[o]: the rows (e, s), Q <= s < active, flattened pair-major, in Pf_o
+ *    parts (fftconv_matrix_sparse_lookahead_far_parts: the same rule on k_o *
+ *    (active - Q) rows; 0 when active <= Q or k_o = 0, and then pre[o] =
+ *    near[o]); contiguous rows per group, groups and parts added ascending, as
+ *    fftconv_matrix_lookahead's far sum.
+ * So (1) a block served from a window and a block that sums everything itself
+ * perform the same operations in the same order: outputs do not depend on the
+ * anchor phase, on fftconv_matrix_sparse_lookahead_set_windows, on how calls
+ * are grouped, or on the load policy; (2) output o is bit-identical to the
+ * single output of a dense fftconv_matrix_lookahead with k_o inputs that holds
+ * the responses h[pair e] and is fed x[i_e] in list order; (3) an output's bits
+ * depend on nothing outside its own pair list and the inputs it names: a
+ * pattern split by outputs over several handles (or GPUs) computes
+ * bit-identical rows.  Results equal fftconv_matrix_sparse's within f32
+ * rounding, not bitwise.
+ * Supported blocks: 32 <= next_power_of_two(max_block_size) <= 512, else
+ * FFTCONV_E_UNSUPPORTED (use fftconv_matrix_sparse there); other errors as
+ * fftconv_matrix_sparse_init.  Everything is reserved at init: update and
+ * update_pairs allocate nothing and do not wait on the host.
+ * Every function below is its fftconv_matrix_sparse_* / fftconv_matrix_lookahead_*
+ * namesake. */
+fftconv_matrix_sparse_lookahead *fftconv_matrix_sparse_lookahead_init(int device, size_t inputs, size_t outputs,
+                                                                      size_t pairs, const uint32_t *pair_out,
+                                                                      const uint32_t *pair_in, const float *responses,
+                                                                      size_t response_len, size_t response_stride,
+                                                                      size_t max_block_size,
+                                                                      size_t max_response_length);
+int fftconv_matrix_sparse_lookahead_update(fftconv_matrix_sparse_lookahead *h, const float *responses,
+                                           size_t response_len, size_t response_stride);
+int fftconv_matrix_sparse_lookahead_update_device(fftconv_matrix_sparse_lookahead *h, const float *d_responses,
+                                                  size_t response_len, size_t response_stride, void *hip_stream);
+int fftconv_matrix_sparse_lookahead_update_pairs(fftconv_matrix_sparse_lookahead *h, size_t n_pairs,
+                                                 const uint32_t *pair_out, const uint32_t *pair_in,
+                                                 const float *responses, size_t response_len, size_t response_stride);
+int fftconv_matrix_sparse_lookahead_update_pairs_device(fftconv_matrix_sparse_lookahead *h, size_t n_pairs,
+                                                        const uint32_t *pair_out, const uint32_t *pair_in,
+                                                        const float *d_responses, size_t response_len,
+                                                        size_t response_stride, void *hip_stream);
+int fftconv_matrix_sparse_lookahead_reset(fftconv_matrix_sparse_lookahead *h); /* :296-306 */
+int fftconv_matrix_sparse_lookahead_process(fftconv_matrix_sparse_lookahead *h, const float *input, size_t input_len,
+                                            float *output, size_t output_len);
+int fftconv_matrix_sparse_lookahead_process_device(fftconv_matrix_sparse_lookahead *h, const float *d_input,
+                                                   size_t in_stride, float *d_output, size_t out_stride, size_t len,
+                                                   void *hip_stream);
+int fftconv_matrix_sparse_lookahead_process_device_steps(fftconv_matrix_sparse_lookahead *h, const float *d_input,
+                                                         size_t in_stride, size_t in_step, float *d_output,
+                                                         size_t out_stride, size_t out_step, size_t len, size_t steps,
+                                                         void *hip_stream);
+/* the clone carries the windows, the plan and the block count: it continues bit for bit */
+fftconv_matrix_sparse_lookahead *fftconv_matrix_sparse_lookahead_clone(const fftconv_matrix_sparse_lookahead *h);
+void fftconv_matrix_sparse_lookahead_destroy(fftconv_matrix_sparse_lookahead *h);
+int fftconv_matrix_sparse_lookahead_synchronize(fftconv_matrix_sparse_lookahead *h);
+size_t fftconv_matrix_sparse_lookahead_inputs(const fftconv_matrix_sparse_lookahead *h);
+size_t fftconv_matrix_sparse_lookahead_outputs(const fftconv_matrix_sparse_lookahead *h);
+size_t fftconv_matrix_sparse_lookahead_pairs(const fftconv_matrix_sparse_lookahead *h);
+size_t fftconv_matrix_sparse_lookahead_block_size(const fftconv_matrix_sparse_lookahead *h);
+size_t fftconv_matrix_sparse_lookahead_seg_count(const fftconv_matrix_sparse_lookahead *h);
+/* {current, active_seg_count, input_buffer_fill} as of the calls enqueued so far */
+int fftconv_matrix_sparse_lookahead_state(const fftconv_matrix_sparse_lookahead *h, size_t out3[3]);
+/* Pn_o and Pf_o of output `output` for the current active_seg_count (0 for a bad index) */
+int fftconv_matrix_sparse_lookahead_near_parts(const fftconv_matrix_sparse_lookahead *h, size_t output);
+int fftconv_matrix_sparse_lookahead_far_parts(const fftconv_matrix_sparse_lookahead *h, size_t output);
+/* on = 0: no output anchors, every block sums its far rows in full (the same bits) */
+int fftconv_matrix_sparse_lookahead_set_windows(fftconv_matrix_sparse_lookahead *h, int on);
+/* outputs with at least one pair that anchor when the next block starts (0
+ * while windows are off, active <= Q or current >= active) */
+int fftconv_matrix_sparse_lookahead_anchors(const fftconv_matrix_sparse_lookahead *h);
 
 /* ---- MatrixCrossfadeConvolver: crossfaded response switching for the matrix ----
  * A matrix crossfade (inputs I, outputs O) behaves as I*O reference
