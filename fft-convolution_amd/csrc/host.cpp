@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/fftconv.h"
+#include "block_walk.hpp"
 #include "kernels.hpp"
 #include "pair_book.hpp"
 
@@ -1924,34 +1925,82 @@ struct CrossfadeCore {
 };
 
 // ---------------------------------------------------------------------------
-// MatrixCore -- I x O FFTConvolver instances (o, i) in lockstep:
-// instance (o, i) processes input i, output o is the sum over i.  One FDL per
-// input shared by all outputs, overlap / pre_multiplied summed per output,
-// one inverse transform per output (matrix.hip).  All instances are created,
-// updated and reset together, so the reference's {current, active_seg_count,
-// input_buffer_fill} (:215-295) is one triple, kept here and advanced when a
-// chunk is enqueued.
+// What the matrix handles' cores share as free functions: `Core` is the
+// handle's core (its process_device), `M` the matrix core that owns the
+// geometry, the stream and the scratch (Core itself, or a lookahead core's m).
 // ---------------------------------------------------------------------------
-struct MatrixCore {
+static_assert(kLookaheadPeriod == kMatrixLaQ, "block_walk.hpp's period is the kernels'");
+
+// a clone's copy of one device buffer, enqueued on s
+template <class T>
+int clone_buffer(DevPtr<T> &dst, const DevPtr<T> &src, hipStream_t s) {
+    if (int r = dst.alloc(src.n)) return r;
+    if (src.n) HIP_TRY(hipMemcpyAsync(dst.p, src.p, src.bytes(), hipMemcpyDeviceToDevice, s));
+    return FFTCONV_OK;
+}
+
+// process() from and to host memory: [I][in_len] -> [O][out_len], the host waits
+template <class Core, class M>
+int matrix_process_host(Core &c, M &m, const float *in, size_t in_len, float *out, size_t out_len) {
+    if (in_len < out_len) return fail(FFTCONV_E_INVALID, "input slice shorter than output (range end index out of range)");
+    if (out_len == 0) return FFTCONV_OK;
+    DeviceGuard g(m.device);
+    if (int r = m.order.enter(m.stream)) return r;
+    if (int r = m.scratch.ensure(m.I * out_len, m.O * out_len)) return r;
+    HIP_TRY(hipMemcpy2DAsync(m.scratch.in.p, out_len * sizeof(float), in, in_len * sizeof(float),
+                             out_len * sizeof(float), m.I, hipMemcpyHostToDevice, m.stream));
+    if (int r = c.process_device(m.scratch.in.p, out_len, m.scratch.out.p, out_len, out_len, m.stream)) return r;
+    HIP_TRY(hipMemcpyAsync(out, m.scratch.out.p, m.O * out_len * sizeof(float), hipMemcpyDeviceToHost, m.stream));
+    HIP_TRY(hipStreamSynchronize(m.stream));
+    return FFTCONV_OK;
+}
+
+// `steps` process_device calls of n samples each, enqueued back to back
+template <class Core>
+int matrix_process_device_steps(Core &c, const float *din, size_t is, size_t in_step, float *dout, size_t os,
+                                size_t out_step, size_t n, size_t steps, hipStream_t s) {
+    for (size_t k = 0; k < steps; ++k)
+        if (int r = c.process_device(din + k * in_step, is, dout + k * out_step, os, n, s)) return r;
+    return FFTCONV_OK;
+}
+
+// ---------------------------------------------------------------------------
+// MatrixBase -- what the dense and the sparse matrix share:
+// P FFTConvolver instances in lockstep, one per (output, input) pair, P = O * I
+// or the N pairs of a pattern.  Instance p processes its pair's input, output o
+// is the sum over its pairs.  One FDL per input shared by all outputs, overlap /
+// pre_multiplied summed per output, one inverse transform per output.  All
+// instances are created, updated and reset together, so the reference's
+// {current, active_seg_count, input_buffer_fill} (:215-295) is one triple
+// (BlockWalk), advanced when a chunk is enqueued.  "Pair" is an index into H
+// [P][S][B], the staging and the pair lists throughout.
+// The concrete core D supplies, each called once per update, never per chunk:
+//   int rebuild_plan(hipStream_t)    active_seg_count was set: what depends on it
+//   int check_list(n, po, pi, idx)   an update_pairs list as ascending pair indices
+// and its own process_device.
+// ---------------------------------------------------------------------------
+template <class D>
+struct MatrixBase : BlockWalk {
     int device = 0;
     size_t I = 0, O = 0;
+    size_t P = 0;         // pairs
     size_t ir_len = 0;    // max_response_length
     size_t B = 0;
     int log2b = 0;
     size_t S = 0;         // seg_count
-    size_t Pmax = 1;      // MAC parts at active = S (the `part` rows per output)
-    size_t cur = 0, act = 0, fill = 0;
     size_t last_len = 0;  // response_len of the last init / update: the length update_pairs pads to
-    DevPtr<float2> H, X, pre, part, tw;
+    DevPtr<float2> H, X, pre, part, tw;  // part: the MAC parts' partial sums, sized by the concrete core
     DevPtr<float> ovl, ib, staging;
     hipStream_t stream = nullptr;
-    bool own_stream = true;  // false: a MatrixCrossfadeCore's / MatrixTwoStageCore's convolver on its owner's stream
+    bool own_stream = true;  // false: a crossfade's / MatrixTwoStageCore's convolver on its owner's stream
     Scratch scratch;
     PinnedStage hstage;
     PairLists lists;      // update_pairs (own_stream only: an owner brings its own)
     mutable StreamOrder order;
 
-    ~MatrixCore() {
+    D &self() { return static_cast<D &>(*this); }
+
+    ~MatrixBase() {
         if (stream && own_stream) {
             DeviceGuard g(device);
             (void)order.drain(stream);
@@ -1959,41 +2008,41 @@ struct MatrixCore {
         }
     }
 
-    int mac_parts() const { return matrix_mac_parts((int)I, log2b, (int)S, (int)act); }
-
-    int alloc_geometry(int dev, size_t inputs, size_t outputs, size_t max_block_size, size_t max_len,
-                       hipStream_t owner = nullptr) {
+    // the sizes (:115-117) and the limits common to both matrices
+    int set_geometry(int dev, size_t inputs, size_t outputs, size_t pairs, size_t max_block_size, size_t max_len) {
         device = dev;
         I = inputs;
         O = outputs;
+        P = pairs;
         ir_len = max_len;
         B = next_pow2(max_block_size);                             // :115
         log2b = ilog2(B);
         if (B < 32 || B > 8192)
             return fail(FFTCONV_E_UNSUPPORTED, "matrix block size " + std::to_string(B) + " outside 32..8192");
         S = ceil_div(ir_len, B);                                   // :117
-        if (S * B > (size_t)INT32_MAX || I > (size_t)INT32_MAX || O > (size_t)INT32_MAX ||
-            I * std::max<size_t>(S, 1) > (size_t)INT32_MAX || O * 64 > (size_t)INT32_MAX)
+        if (S * B > (size_t)INT32_MAX || I * std::max<size_t>(S, 1) > (size_t)INT32_MAX)
             return fail(FFTCONV_E_UNSUPPORTED, "geometry exceeds 32-bit indexing");
         act = S;
-        Pmax = (size_t)matrix_mac_parts((int)I, log2b, (int)S, (int)S);
+        return FFTCONV_OK;
+    }
+    // the stream (`owner`: the matrix runs on that stream), the buffers of the
+    // block walk (`part` of part_count spectra) and the twiddle table.  (The
+    // order of the allocations is kept as it has always been: the buffers'
+    // placement is worth a percent of a block's time.)
+    int alloc_walk(hipStream_t owner, size_t part_count) {
         if (owner) {
             stream = owner;
             own_stream = false;
         } else {
             HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         }
-        if (int r = H.alloc(O * I * S * B)) return r;
+        if (int r = H.alloc(P * S * B)) return r;
         if (int r = X.alloc(I * S * B)) return r;
         if (int r = pre.alloc(O * B)) return r;
-        if (int r = part.alloc(O * Pmax * B)) return r;
+        if (int r = part.alloc(part_count * B)) return r;
         if (int r = ovl.alloc(O * B)) return r;
         if (int r = ib.alloc(I * B)) return r;
         if (int r = tw.alloc(2 * B)) return r;
-        if (int r = staging.alloc(O * I * ir_len)) return r;       // update() never allocates
-        if (int r = hstage.alloc(O * I * ir_len, ir_len)) return r;
-        if (!owner)
-            if (int r = lists.alloc(O * I)) return r;
         std::vector<float2> t(2 * B);
         const size_t N = 2 * B;
         for (size_t k = 0; k < N; ++k) {
@@ -2003,12 +2052,18 @@ struct MatrixCore {
         HIP_TRY(hipMemcpy(tw.p, t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice));
         return FFTCONV_OK;
     }
+    // what update() and update_pairs() stage through: update() never allocates
+    int alloc_staging() {
+        if (int r = staging.alloc(P * ir_len)) return r;
+        if (int r = hstage.alloc(P * ir_len, ir_len)) return r;
+        return own_stream ? lists.alloc(P) : FFTCONV_OK;
+    }
 
     // the IR transform of every pair from device samples (pair p at src +
     // p * stride): rows at or past ceil(len_active / B) are zeroed (:210-212)
     int ir_from_device(const float *src, size_t stride, size_t len_data, size_t len_active, hipStream_t s) {
-        const size_t pairs = O * I, step = 32768;  // (grid.y of the transform)
-        for (size_t p0 = 0; p0 < pairs; p0 += step) {
+        const size_t step = 32768;  // (grid.y of the transform)
+        for (size_t p0 = 0; p0 < P; p0 += step) {
             IrArgs a{};
             a.H = H.p;
             a.src = src + p0 * stride;
@@ -2019,7 +2074,7 @@ struct MatrixCore {
             a.S = (int)S;
             a.chan0 = (int)p0;
             a.update_state = 0;
-            HIP_TRY(launch_ir_segments(log2b, a, (int)std::min(step, pairs - p0), s));
+            HIP_TRY(launch_ir_segments(log2b, a, (int)std::min(step, P - p0), s));
         }
         return FFTCONV_OK;
     }
@@ -2033,26 +2088,26 @@ struct MatrixCore {
         fill = 0;
         return FFTCONV_OK;
     }
+    int reset(hipStream_t s) { return zero_state(s); }
 
-    // `owner`: the matrix is a stage of a MatrixTwoStageCore and runs on that stream
-    int init(int dev, size_t inputs, size_t outputs, const float *responses, size_t len, size_t stride,
-             size_t max_block, size_t max_len, hipStream_t owner = nullptr) {
-        if (inputs == 0 || outputs == 0) return fail(FFTCONV_E_INVALID, "a matrix needs at least one input and one output");
-        if (max_len < len)                                          // :106-110
-            return fail(FFTCONV_E_INVALID,
-                        "max_response_length must be at least the length of the initial impulse response");
-        if (int r = check_device(dev)) return r;
-        DeviceGuard g(dev);
-        if (int r = alloc_geometry(dev, inputs, outputs, max_block, max_len, owner)) return r;
-        if (int r = zero_state(stream)) return r;
+    // the end of init: the initial responses' transforms (:119-172), then the host waits
+    int init_responses(const float *responses, size_t len, size_t stride) {
         last_len = len;
         if (S > 0) {
-            const bool shared = stride == 0 && O * I > 1;
+            const bool shared = stride == 0 && P > 1;
             if (len)
-                if (int r = hstage.upload(responses, shared ? 1 : O * I, len, stride, staging.p, ir_len, stream)) return r;
+                if (int r = hstage.upload(responses, shared ? 1 : P, len, stride, staging.p, ir_len, stream)) return r;
             if (int r = ir_from_device(staging.p, shared ? 0 : ir_len, len, ir_len, stream)) return r;
         }
         HIP_TRY(hipStreamSynchronize(stream));
+        return FFTCONV_OK;
+    }
+
+    // update's side effects on the state (:186-190; current untouched)
+    int set_active(size_t active, hipStream_t s) {
+        if (pre.n) HIP_TRY(hipMemsetAsync(pre.p, 0, pre.bytes(), s));   // :187
+        if (ovl.n) HIP_TRY(hipMemsetAsync(ovl.p, 0, ovl.bytes(), s));   // :188
+        act = active;                                                   // :190
         return FFTCONV_OK;
     }
 
@@ -2061,10 +2116,9 @@ struct MatrixCore {
     int update_device(const float *src, size_t stride, size_t len, hipStream_t s) {
         if (len > ir_len) return fail(FFTCONV_E_INVALID, "New impulse response is longer than initialized length");
         if (ir_len == 0) return FFTCONV_OK;                         // :181-183
-        if (pre.n) HIP_TRY(hipMemsetAsync(pre.p, 0, pre.bytes(), s));   // :187
-        if (ovl.n) HIP_TRY(hipMemsetAsync(ovl.p, 0, ovl.bytes(), s));   // :188
-        act = ceil_div(len, B);                                     // :190 (current untouched)
+        if (int r = set_active(ceil_div(len, B), s)) return r;
         last_len = len;
+        if (int r = self().rebuild_plan(s)) return r;
         return ir_from_device(src, stride, len, len, s);
     }
     int update_host(const float *src, size_t len, size_t stride) {
@@ -2072,17 +2126,17 @@ struct MatrixCore {
         if (ir_len == 0) return FFTCONV_OK;
         DeviceGuard g(device);
         if (int r = order.enter(stream)) return r;
-        const bool shared = stride == 0 && O * I > 1;
+        const bool shared = stride == 0 && P > 1;
         if (len)
-            if (int r = hstage.upload(src, shared ? 1 : O * I, len, stride, staging.p, ir_len, stream)) return r;
+            if (int r = hstage.upload(src, shared ? 1 : P, len, stride, staging.p, ir_len, stream)) return r;
         return update_device(staging.p, shared ? 0 : ir_len, len, stream);
     }
 
-    // One patch of H (matrix_patch.hip) from the lists staged in L's mirror:
-    // the first n_tr pairs of L.tr() are transformed from `src` (entry n reads
-    // row n, or -- by_pair -- the row of its pair index), the first n_cp pairs
-    // of L.cp() are copied from Hsrc.  One launch up to kMatrixPatchChunk pairs
-    // per list.
+    // One patch of H (matrix_patch.hip, generic in the pair index) from the
+    // lists staged in L's mirror: the first n_tr pairs of L.tr() are
+    // transformed from `src` (entry n reads row n, or -- by_pair -- the row of
+    // its pair index), the first n_cp pairs of L.cp() are copied from Hsrc.
+    // One launch up to kMatrixPatchChunk pairs per list.
     int patch_device(PairLists &L, size_t n_tr, size_t n_cp, const float2 *Hsrc, const float *src, size_t stride,
                      bool by_pair, size_t len_data, size_t len_active, hipStream_t s) {
         if (int r = L.push(n_tr, n_cp, s)) return r;
@@ -2103,7 +2157,7 @@ struct MatrixCore {
             a.row0 = (int)c0;
             a.by_pair = by_pair ? 1 : 0;
             a.S = (int)S;
-            a.pairs = (int)(O * I);
+            a.pairs = (int)P;
             a.nt_cp = Variant::current().nt_matrix(H.bytes()) ? 1 : 0;
             HIP_TRY(launch_matrix_patch(log2b, a, s));
         }
@@ -2112,24 +2166,21 @@ struct MatrixCore {
 
     // update(R'), R' = the responses this matrix holds with the n listed pairs
     // (ascending, in L.tr()) replaced by rows 0..n-1 of src, at the length of
-    // the last init / update: update's side effects, and only the
-    // listed pairs are transformed -- every other pair's rows are already the
-    // ones update(R') would write.
+    // the last init / update: update's side effects (the plan
+    // included), and only the listed pairs are transformed -- every other
+    // pair's rows are already the ones update(R') would write.
     int update_pairs_device(PairLists &L, size_t n, const float *src, size_t stride, size_t len, hipStream_t s) {
         if (len > last_len)
             return fail(FFTCONV_E_INVALID, "update_pairs: response longer than the length the response set was applied at");
         if (ir_len == 0) return FFTCONV_OK;
-        if (pre.n) HIP_TRY(hipMemsetAsync(pre.p, 0, pre.bytes(), s));
-        if (ovl.n) HIP_TRY(hipMemsetAsync(ovl.p, 0, ovl.bytes(), s));
-        act = ceil_div(last_len, B);
+        if (int r = set_active(ceil_div(last_len, B), s)) return r;
+        if (int r = self().rebuild_plan(s)) return r;
         return patch_device(L, n, 0, nullptr, src, stride, false, len, last_len, s);
     }
     // the C ABI's two variants: d_src == false -- host rows through the pinned staging
     int update_pairs(size_t n, const uint32_t *pair_out, const uint32_t *pair_in, const float *src, bool d_src,
                      size_t len, size_t stride, hipStream_t s) {
-        if (n && (!pair_out || !pair_in)) return fail(FFTCONV_E_INVALID, "null pair list");
-        if (n > O * I) return fail(FFTCONV_E_INVALID, "the pair list must be strictly ascending in (output, input)");
-        if (PairListError e = check_pairs(n, pair_out, pair_in, I, O, lists.idx.data())) return pair_list_error(e);
+        if (int r = self().check_list(n, pair_out, pair_in, lists.idx.data())) return r;
         if (len > last_len)
             return fail(FFTCONV_E_INVALID, "update_pairs: response longer than the length the response set was applied at");
         DeviceGuard g(device);
@@ -2144,93 +2195,145 @@ struct MatrixCore {
         return update_pairs_device(lists, n, src, stride, len, s);
     }
 
-    int process_device(const float *din, size_t is, float *dout, size_t os, size_t n, hipStream_t s) {
+    // What every process_device starts with.  *launch = false: nothing to
+    // enqueue -- no samples, or active_seg_count == 0 (:216-219: zero output,
+    // state untouched).
+    int process_begin(float *dout, size_t os, size_t n, hipStream_t s, bool *launch) const {
+        *launch = false;
         if (n > (size_t)INT32_MAX) return fail(FFTCONV_E_UNSUPPORTED, "process length exceeds 2^31-1");
         if (n == 0) return FFTCONV_OK;
-        if (act == 0) {  // :216-219 -- zero output, state untouched
+        if (act == 0) {
             HIP_TRY(hipMemset2DAsync(dout, os * sizeof(float), 0, n * sizeof(float), O, s));
             return FFTCONV_OK;
         }
-        MatrixArgs a{};
-        a.H = H.p; a.X = X.p; a.ovl = ovl.p; a.ib = ib.p; a.pre = pre.p; a.part = part.p; a.tw = tw.p;
+        *launch = true;
+        return FFTCONV_OK;
+    }
+    // the call's part of a chunk launch's arguments (`part` and the part counts are the caller's)
+    void call_args(MatrixArgs &a, size_t is, size_t os) const {
+        a.H = H.p; a.X = X.p; a.ovl = ovl.p; a.ib = ib.p; a.pre = pre.p; a.tw = tw.p;
         a.in_stride = (long long)is;
         a.out_stride = (long long)os;
         a.I = (int)I; a.O = (int)O; a.S = (int)S;
-        a.P = mac_parts();
-        const size_t R = I * (act - 1);
-        a.rpp = (int)ceil_div(R, (size_t)a.P);
         a.act = (int)act;
         a.nt_h = Variant::current().nt_matrix(H.bytes()) ? 1 : 0;
-        size_t processed = 0;
-        while (processed < n) {                                     // :222-294
-            const size_t k = std::min(n - processed, B - fill);     // :224-227
-            a.in = din + processed;
-            a.out = dout + processed;
-            a.cur = (int)cur;
-            a.fill = (int)fill;
-            a.k = (int)k;
-            HIP_TRY(launch_matrix_chunk(log2b, a, s));
-            fill += k;
-            if (fill == B) {                                        // :277-291
-                fill = 0;
-                cur = cur > 0 ? cur - 1 : act - 1;
-            }
-            processed += k;
-        }
-        return FFTCONV_OK;
     }
-
-    int process_device_steps(const float *din, size_t is, size_t in_step, float *dout, size_t os, size_t out_step,
-                             size_t n, size_t steps, hipStream_t s) {
-        for (size_t k = 0; k < steps; ++k)
-            if (int r = process_device(din + k * in_step, is, dout + k * out_step, os, n, s)) return r;
-        return FFTCONV_OK;
+    // the next chunk (:224-227) of a call with `done` of its n samples enqueued
+    size_t chunk_args(MatrixArgs &a, const float *din, float *dout, size_t done, size_t n) const {
+        const size_t k = chunk(n - done, B);
+        a.in = din + done;
+        a.out = dout + done;
+        a.cur = (int)cur;
+        a.fill = (int)fill;
+        a.k = (int)k;
+        return k;
     }
 
     int process_host(const float *in, size_t in_len, float *out, size_t out_len) {
-        if (in_len < out_len) return fail(FFTCONV_E_INVALID, "input slice shorter than output (range end index out of range)");
-        if (out_len == 0) return FFTCONV_OK;
-        DeviceGuard g(device);
-        if (int r = order.enter(stream)) return r;
-        if (int r = scratch.ensure(I * out_len, O * out_len)) return r;
-        HIP_TRY(hipMemcpy2DAsync(scratch.in.p, out_len * sizeof(float), in, in_len * sizeof(float),
-                                 out_len * sizeof(float), I, hipMemcpyHostToDevice, stream));
-        if (int r = process_device(scratch.in.p, out_len, scratch.out.p, out_len, out_len, stream)) return r;
-        HIP_TRY(hipMemcpyAsync(out, scratch.out.p, O * out_len * sizeof(float), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        return FFTCONV_OK;
+        return matrix_process_host(self(), *this, in, in_len, out, out_len);
     }
 
-    // #[derive(Clone)]; `owner`: the clone is a MatrixCrossfadeCore's convolver
-    // -- it runs on that stream and stages updates through its owner
-    int clone_from(const MatrixCore &o, hipStream_t owner = nullptr) {
-        DeviceGuard g(o.device);
+    // #[derive(Clone)] of the base's part; `owner`: the clone is a crossfade's
+    // convolver -- it runs on that stream and stages updates through its owner.
+    // (The caller waits for the stream.)
+    int clone_base(const MatrixBase &o, hipStream_t owner) {
         if (int r = o.order.drain(o.stream)) return r;
         device = o.device;
-        I = o.I; O = o.O; ir_len = o.ir_len; B = o.B; log2b = o.log2b; S = o.S; Pmax = o.Pmax;
+        I = o.I; O = o.O; P = o.P; ir_len = o.ir_len; B = o.B; log2b = o.log2b; S = o.S;
         cur = o.cur; act = o.act; fill = o.fill; last_len = o.last_len;
         if (owner) {
             stream = owner;
             own_stream = false;
         } else {
             HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-            if (int r = lists.alloc(O * I)) return r;
+            if (int r = lists.alloc(P)) return r;
         }
-        auto cp = [&](auto &dst, const auto &src) -> int {
-            if (int r = dst.alloc(src.n)) return r;
-            if (src.n) HIP_TRY(hipMemcpyAsync(dst.p, src.p, src.bytes(), hipMemcpyDeviceToDevice, stream));
-            return FFTCONV_OK;
-        };
-        if (int r = cp(H, o.H)) return r;
-        if (int r = cp(X, o.X)) return r;
-        if (int r = cp(pre, o.pre)) return r;
-        if (int r = cp(tw, o.tw)) return r;
-        if (int r = cp(ovl, o.ovl)) return r;
-        if (int r = cp(ib, o.ib)) return r;
+        if (int r = clone_buffer(H, o.H, stream)) return r;
+        if (int r = clone_buffer(X, o.X, stream)) return r;
+        if (int r = clone_buffer(pre, o.pre, stream)) return r;
+        if (int r = clone_buffer(tw, o.tw, stream)) return r;
+        if (int r = clone_buffer(ovl, o.ovl, stream)) return r;
+        return clone_buffer(ib, o.ib, stream);
+    }
+    // ... and what a clone reserves without copying, after the concrete core's own buffers
+    int clone_reserve(const MatrixBase &o) {
         if (int r = part.alloc(o.part.n)) return r;  // (rewritten by every block before it is read)
         if (int r = staging.alloc(o.staging.n)) return r;
-        if (!owner)
-            if (int r = hstage.alloc(o.hstage.n, ir_len)) return r;
+        return own_stream ? hstage.alloc(o.hstage.n, ir_len) : FFTCONV_OK;
+    }
+};
+
+// ---------------------------------------------------------------------------
+// MatrixCore -- the dense matrix (matrix.hip): pair (o, i) is
+// o * I + i, every output sums all I inputs.
+// ---------------------------------------------------------------------------
+struct MatrixCore : MatrixBase<MatrixCore> {
+    static constexpr const char *kName = "matrix";
+    using XfArgs = MatrixXfArgs;
+    size_t Pmax = 1;      // MAC parts at active = S (the `part` rows per output)
+
+    int mac_parts() const { return matrix_mac_parts((int)I, log2b, (int)S, (int)act); }
+    int rebuild_plan(hipStream_t) { return FFTCONV_OK; }  // (the MAC grid is a function of active alone)
+
+    int check_list(size_t n, const uint32_t *pair_out, const uint32_t *pair_in, uint32_t *idx) const {
+        if (n && (!pair_out || !pair_in)) return fail(FFTCONV_E_INVALID, "null pair list");
+        if (n > P) return fail(FFTCONV_E_INVALID, "the pair list must be strictly ascending in (output, input)");
+        if (PairListError e = check_pairs(n, pair_out, pair_in, I, O, idx)) return pair_list_error(e);
+        return FFTCONV_OK;
+    }
+
+    int alloc_geometry(int dev, size_t inputs, size_t outputs, size_t max_block_size, size_t max_len, hipStream_t owner) {
+        if (int r = set_geometry(dev, inputs, outputs, inputs * outputs, max_block_size, max_len)) return r;
+        if (I > (size_t)INT32_MAX || O > (size_t)INT32_MAX || O * 64 > (size_t)INT32_MAX)
+            return fail(FFTCONV_E_UNSUPPORTED, "geometry exceeds 32-bit indexing");
+        Pmax = (size_t)matrix_mac_parts((int)I, log2b, (int)S, (int)S);
+        if (int r = alloc_walk(owner, O * Pmax)) return r;
+        return alloc_staging();
+    }
+
+    // `owner`: the matrix is a stage of a MatrixTwoStageCore and runs on that stream
+    int init(int dev, size_t inputs, size_t outputs, const float *responses, size_t len, size_t stride,
+             size_t max_block, size_t max_len, hipStream_t owner = nullptr) {
+        if (inputs == 0 || outputs == 0) return fail(FFTCONV_E_INVALID, "a matrix needs at least one input and one output");
+        if (max_len < len)                                          // :106-110
+            return fail(FFTCONV_E_INVALID,
+                        "max_response_length must be at least the length of the initial impulse response");
+        if (int r = check_device(dev)) return r;
+        DeviceGuard g(dev);
+        if (int r = alloc_geometry(dev, inputs, outputs, max_block, max_len, owner)) return r;
+        if (int r = zero_state(stream)) return r;
+        return init_responses(responses, len, stride);
+    }
+
+    int process_device(const float *din, size_t is, float *dout, size_t os, size_t n, hipStream_t s) {
+        bool launch;
+        if (int r = process_begin(dout, os, n, s, &launch); r || !launch) return r;
+        MatrixArgs a{};
+        call_args(a, is, os);
+        a.part = part.p;
+        a.P = mac_parts();
+        a.rpp = (int)ceil_div(I * (act - 1), (size_t)a.P);
+        for (size_t done = 0; done < n;) {                          // :222-294
+            const size_t k = chunk_args(a, din, dout, done, n);
+            HIP_TRY(launch_matrix_chunk(log2b, a, s));
+            advance(k, B);
+            done += k;
+        }
+        return FFTCONV_OK;
+    }
+
+    // the fused crossfade launch (matrix_xf.hip): what it takes beyond the shared arguments
+    void xf_args(XfArgs &x) const {
+        x.P = mac_parts();
+        x.rpp = (int)ceil_div(I * (act - 1), (size_t)x.P);
+    }
+    static hipError_t launch_xf_chunk(int log2b, const XfArgs &x, hipStream_t s) { return launch_matrix_xf_chunk(log2b, x, s); }
+
+    int clone_from(const MatrixCore &o, hipStream_t owner = nullptr) {  // #[derive(Clone)]
+        DeviceGuard g(o.device);
+        if (int r = clone_base(o, owner)) return r;
+        Pmax = o.Pmax;
+        if (int r = clone_reserve(o)) return r;
         HIP_TRY(hipStreamSynchronize(stream));
         return FFTCONV_OK;
     }
@@ -2240,18 +2343,13 @@ struct MatrixCore {
 // MatrixLookaheadCore -- the MatrixCore's I x O instances with one level of
 // far-row windows (matrix_la.hip).  The dense core `m` owns the
 // geometry, the buffers, the stream and {current, active, fill}; this core adds
-// the near / far partial sums and the block count that schedules the anchors.
-//   t   blocks started since init (the block the next fill == 0 chunk starts)
-//   tv  windows anchored before block tv are invalid: init, reset, update and
-//       every block that starts with current >= active (or with the windows
-//       switched off) move it past every anchor made so far
+// the near / far partial sums and the block clock that schedules the anchors.
 // ---------------------------------------------------------------------------
 struct MatrixLookaheadCore {
     static constexpr size_t Q = kMatrixLaQ;
     MatrixCore m;
     DevPtr<float2> far;  // [O][Pf_max][Q][B]; the near partial sums use m.part (Pn <= the dense P)
-    long long t = 0, tv = 0;
-    bool windows = true;
+    LookaheadClock clk;
 
     // rows (i, s) of one output: near 1 <= s < min(Q, active), far Q <= s < active
     size_t near_rows() const { return m.I * (std::min(m.act, Q) > 0 ? std::min(m.act, Q) - 1 : 0); }
@@ -2260,14 +2358,10 @@ struct MatrixLookaheadCore {
     int far_parts() const { return far_rows() ? matrix_la_parts((long long)far_rows()) : 0; }
     // outputs that anchor when the next block starts
     int anchors() const {
-        if (!windows || m.act <= Q || m.cur >= m.act) return 0;
-        const size_t t0 = (size_t)(t % (long long)Q);
+        if (!clk.windows || m.act <= Q || m.cur >= m.act) return 0;
+        const size_t t0 = (size_t)(clk.t % (long long)Q);
         return t0 < m.O ? (int)((m.O - t0 + Q - 1) / Q) : 0;
     }
-
-    // no anchor made so far counts from here on; the block in progress (fill >
-    // 0) has made its anchors already, so they are past too
-    void invalidate() { tv = m.fill ? t + 1 : t; }
 
     int alloc_extra() {
         const size_t pf = m.S > Q ? (size_t)matrix_la_parts((long long)m.I * (long long)(m.S - Q)) : 0;
@@ -2281,144 +2375,82 @@ struct MatrixLookaheadCore {
                                                    " outside 32..512 (use the MatrixConvolver)");
         if (int r = m.init(dev, inputs, outputs, responses, len, stride, max_block, max_len)) return r;
         DeviceGuard g(dev);
-        t = tv = 0;
+        clk = LookaheadClock();
         return alloc_extra();
     }
     int update_device(const float *src, size_t stride, size_t len, hipStream_t s) {
         if (int r = m.update_device(src, stride, len, s)) return r;
-        invalidate();
+        clk.invalidate(m.fill);
         return FFTCONV_OK;
     }
     int update_host(const float *src, size_t len, size_t stride) {
         if (int r = m.update_host(src, len, stride)) return r;
-        invalidate();
+        clk.invalidate(m.fill);
         return FFTCONV_OK;
     }
     int reset(hipStream_t s) {
-        if (m.fill) ++t;  // (the block in progress is dropped: its number is not used again)
+        const size_t fill = m.fill;  // (zero_state clears it)
         if (int r = m.zero_state(s)) return r;
-        invalidate();
+        clk.reset(fill);
         return FFTCONV_OK;
     }
 
     int process_device(const float *din, size_t is, float *dout, size_t os, size_t n, hipStream_t s) {
-        if (n > (size_t)INT32_MAX) return fail(FFTCONV_E_UNSUPPORTED, "process length exceeds 2^31-1");
-        if (n == 0) return FFTCONV_OK;
-        if (m.act == 0) {  // :216-219 -- zero output, state untouched
-            HIP_TRY(hipMemset2DAsync(dout, os * sizeof(float), 0, n * sizeof(float), m.O, s));
-            return FFTCONV_OK;
-        }
+        bool launch;
+        if (int r = m.process_begin(dout, os, n, s, &launch); r || !launch) return r;
         MatrixLaArgs la{};
         MatrixArgs &a = la.m;
-        a.H = m.H.p; a.X = m.X.p; a.ovl = m.ovl.p; a.ib = m.ib.p; a.pre = m.pre.p; a.part = m.part.p; a.tw = m.tw.p;
-        a.in_stride = (long long)is;
-        a.out_stride = (long long)os;
-        a.I = (int)m.I; a.O = (int)m.O; a.S = (int)m.S;
+        // nt_h by the whole H, as the dense matrix: a block streams 1 / Q of the
+        // far rows, but over Q blocks all of H passes through the cache (measured,
+        // DESIGN 4n: judging by a block's own bytes chose plain loads at M2 and lost 6 %)
+        m.call_args(a, is, os);
+        a.part = m.part.p;
         a.P = near_parts();
         a.rpp = (int)ceil_div(near_rows(), (size_t)a.P);
-        a.act = (int)m.act;
         la.far = far.p;
         la.Pf = far_parts();
         la.rppf = la.Pf ? (int)ceil_div(far_rows(), (size_t)la.Pf) : 0;
-        // by the whole H, as the dense matrix: a block streams 1 / Q of the far
-        // rows, but over Q blocks all of H passes through the cache (measured,
-        // DESIGN 4n: judging by a block's own bytes chose plain loads at M2 and lost 6 %)
-        a.nt_h = Variant::current().nt_matrix(m.H.bytes()) ? 1 : 0;
-        size_t processed = 0;
-        while (processed < n) {                                     // :222-294
-            const size_t k = std::min(n - processed, m.B - m.fill); // :224-227
-            if (m.fill == 0 && (!windows || m.cur >= m.act)) tv = t + 1;  // no anchor in this block
-            a.in = din + processed;
-            a.out = dout + processed;
-            a.cur = (int)m.cur;
-            a.fill = (int)m.fill;
-            a.k = (int)k;
-            la.t = t;
-            la.tv = tv;
+        for (size_t done = 0; done < n;) {                          // :222-294
+            clk.begin_chunk(m.fill, m.cur, m.act);
+            const size_t k = m.chunk_args(a, din, dout, done, n);
+            la.t = clk.t;
+            la.tv = clk.tv;
             HIP_TRY(launch_matrix_la_chunk(m.log2b, la, s));
-            m.fill += k;
-            if (m.fill == m.B) {                                    // :277-291
-                m.fill = 0;
-                m.cur = m.cur > 0 ? m.cur - 1 : m.act - 1;
-                ++t;
-            }
-            processed += k;
+            if (m.advance(k, m.B)) clk.block_done();
+            done += k;
         }
-        return FFTCONV_OK;
-    }
-
-    int process_device_steps(const float *din, size_t is, size_t in_step, float *dout, size_t os, size_t out_step,
-                             size_t n, size_t steps, hipStream_t s) {
-        for (size_t k = 0; k < steps; ++k)
-            if (int r = process_device(din + k * in_step, is, dout + k * out_step, os, n, s)) return r;
         return FFTCONV_OK;
     }
 
     int process_host(const float *in, size_t in_len, float *out, size_t out_len) {
-        if (in_len < out_len) return fail(FFTCONV_E_INVALID, "input slice shorter than output (range end index out of range)");
-        if (out_len == 0) return FFTCONV_OK;
-        DeviceGuard g(m.device);
-        if (int r = m.order.enter(m.stream)) return r;
-        if (int r = m.scratch.ensure(m.I * out_len, m.O * out_len)) return r;
-        HIP_TRY(hipMemcpy2DAsync(m.scratch.in.p, out_len * sizeof(float), in, in_len * sizeof(float),
-                                 out_len * sizeof(float), m.I, hipMemcpyHostToDevice, m.stream));
-        if (int r = process_device(m.scratch.in.p, out_len, m.scratch.out.p, out_len, out_len, m.stream)) return r;
-        HIP_TRY(hipMemcpyAsync(out, m.scratch.out.p, m.O * out_len * sizeof(float), hipMemcpyDeviceToHost, m.stream));
-        HIP_TRY(hipStreamSynchronize(m.stream));
-        return FFTCONV_OK;
+        return matrix_process_host(*this, m, in, in_len, out, out_len);
     }
 
-    int clone_from(const MatrixLookaheadCore &o) {  // #[derive(Clone)]: the windows and {t, tv} too
+    int clone_from(const MatrixLookaheadCore &o) {  // #[derive(Clone)]: the windows and the clock too
         if (int r = m.clone_from(o.m)) return r;
         DeviceGuard g(m.device);
-        t = o.t;
-        tv = o.tv;
-        windows = o.windows;
-        if (int r = far.alloc(o.far.n)) return r;
-        if (far.n) HIP_TRY(hipMemcpyAsync(far.p, o.far.p, far.bytes(), hipMemcpyDeviceToDevice, m.stream));
+        clk = o.clk;
+        if (int r = clone_buffer(far, o.far, m.stream)) return r;
         HIP_TRY(hipStreamSynchronize(m.stream));
         return FFTCONV_OK;
     }
 };
 
 // ---------------------------------------------------------------------------
-// SparseMatrixCore -- N FFTConvolver instances in lockstep, one per listed
-// (output, input) pair: the MatrixCore's scheme over a CSR
-// pattern that is fixed for the life of the handle.  H, the staging and the
-// IR transforms cover the N pairs only; launch A's MAC grid is the compact
-// sum of the outputs' P_o, found through a device plan that is rebuilt on the
-// stream whenever active_seg_count changes (init, update).
+// SparseMatrixCore -- the matrix over a CSR pattern that is fixed for the life
+// of the handle (matrix_sp.hip): pair n is the n-th listed (output,
+// input), P = N.  Launch A's MAC grid is the compact sum of the outputs' P_o,
+// found through a device plan that is rebuilt on the stream whenever
+// active_seg_count is set (init, update, update_pairs).
 // ---------------------------------------------------------------------------
-struct SparseMatrixCore {
-    int device = 0;
-    size_t I = 0, O = 0, N = 0;
-    size_t ir_len = 0;    // max_response_length
-    size_t B = 0;
-    int log2b = 0;
-    size_t S = 0;         // seg_count
+struct SparseMatrixCore : MatrixBase<SparseMatrixCore> {
+    static constexpr const char *kName = "sparse matrix";
+    using XfArgs = MatrixSpXfArgs;
     size_t PTmax = 0;     // sum of P_o at active = S (the rows of `part`)
     size_t PT = 0;        // sum of P_o at the current active
-    size_t cur = 0, act = 0, fill = 0;
-    size_t last_len = 0;  // response_len of the last init / update: the length update_pairs pads to
     std::vector<int> rowptr, col;  // the host's copy of the pattern
-    DevPtr<float2> H, X, pre, part, tw;
-    DevPtr<float> ovl, ib, staging;
     DevPtr<int> d_rowptr, d_col, plan;
     DevPtr<int4> wg;      // [PTmax] the MAC workgroups' descriptors, rebuilt with the plan
-    hipStream_t stream = nullptr;
-    bool own_stream = true;  // false: a SparseMatrixCrossfadeCore's convolver on its owner's stream
-    Scratch scratch;
-    PinnedStage hstage;
-    PairLists lists;      // update_pairs (own_stream only: an owner brings its own)
-    mutable StreamOrder order;
-
-    ~SparseMatrixCore() {
-        if (stream && own_stream) {
-            DeviceGuard g(device);
-            (void)order.drain(stream);
-            (void)hipStreamDestroy(stream);
-        }
-    }
 
     size_t pairs_of(size_t o) const { return (size_t)(rowptr[o + 1] - rowptr[o]); }
     int output_parts(size_t o) const { return matrix_mac_parts((int)pairs_of(o), log2b, (int)S, (int)act); }
@@ -2451,77 +2483,32 @@ struct SparseMatrixCore {
         return FFTCONV_OK;
     }
 
+    // the pair list of an update_pairs call as positions in the pattern's list
+    int check_list(size_t n, const uint32_t *pair_out, const uint32_t *pair_in, uint32_t *idx) const {
+        if (n && (!pair_out || !pair_in)) return fail(FFTCONV_E_INVALID, "null pair list");
+        if (n > P) return fail(FFTCONV_E_INVALID, "the pair list must be strictly ascending in (output, input)");
+        size_t bad = 0;
+        const PairListError e = check_pairs_in_pattern(n, pair_out, pair_in, rowptr.data(), col.data(), I, O, idx, &bad);
+        if (e == PAIRS_ABSENT)
+            return fail(FFTCONV_E_INVALID, "pair (" + std::to_string(pair_out[bad]) + ", " + std::to_string(pair_in[bad]) +
+                                               ") is not in the pattern");
+        return e ? pair_list_error(e) : FFTCONV_OK;
+    }
+
     int alloc_geometry(int dev, size_t inputs, size_t outputs, size_t pairs, size_t max_block_size, size_t max_len) {
-        device = dev;
-        I = inputs;
-        O = outputs;
-        N = pairs;
-        ir_len = max_len;
-        B = next_pow2(max_block_size);                             // :115
-        log2b = ilog2(B);
-        if (B < 32 || B > 8192)
-            return fail(FFTCONV_E_UNSUPPORTED, "matrix block size " + std::to_string(B) + " outside 32..8192");
-        S = ceil_div(ir_len, B);                                   // :117
-        if (S * B > (size_t)INT32_MAX || I * std::max<size_t>(S, 1) > (size_t)INT32_MAX ||
-            N * std::max<size_t>(S, 1) > (size_t)INT32_MAX)
+        if (int r = set_geometry(dev, inputs, outputs, pairs, max_block_size, max_len)) return r;
+        if (P * std::max<size_t>(S, 1) > (size_t)INT32_MAX)
             return fail(FFTCONV_E_UNSUPPORTED, "geometry exceeds 32-bit indexing");
-        act = S;
         PTmax = total_parts(S);
         if (I + PTmax > (size_t)INT32_MAX) return fail(FFTCONV_E_UNSUPPORTED, "geometry exceeds 32-bit indexing");
-        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        if (int r = H.alloc(N * S * B)) return r;
-        if (int r = X.alloc(I * S * B)) return r;
-        if (int r = pre.alloc(O * B)) return r;
-        if (int r = part.alloc(PTmax * B)) return r;               // (P_o is largest at active = S)
-        if (int r = ovl.alloc(O * B)) return r;
-        if (int r = ib.alloc(I * B)) return r;
-        if (int r = tw.alloc(2 * B)) return r;
+        if (int r = alloc_walk(nullptr, PTmax)) return r;          // (P_o is largest at active = S)
         if (int r = d_rowptr.alloc(O + 1)) return r;
-        if (int r = d_col.alloc(N)) return r;
+        if (int r = d_col.alloc(P)) return r;
         if (int r = plan.alloc(O + 1)) return r;
         if (int r = wg.alloc(PTmax)) return r;
-        if (int r = staging.alloc(N * ir_len)) return r;           // update() never allocates
-        if (int r = hstage.alloc(N * ir_len, ir_len)) return r;
-        if (int r = lists.alloc(N)) return r;
-        std::vector<float2> t(2 * B);
-        const size_t NN = 2 * B;
-        for (size_t k = 0; k < NN; ++k) {
-            const double ang = -2.0 * M_PI * (double)k / (double)NN;
-            t[k] = make_float2((float)std::cos(ang), (float)std::sin(ang));
-        }
-        HIP_TRY(hipMemcpy(tw.p, t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice));
+        if (int r = alloc_staging()) return r;
         HIP_TRY(hipMemcpy(d_rowptr.p, rowptr.data(), d_rowptr.bytes(), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_col.p, col.data(), d_col.bytes(), hipMemcpyHostToDevice));
-        return FFTCONV_OK;
-    }
-
-    // the IR transform of every listed pair from device samples (pair n at src
-    // + n * stride): rows at or past ceil(len_active / B) are zeroed (:210-212)
-    int ir_from_device(const float *src, size_t stride, size_t len_data, size_t len_active, hipStream_t s) {
-        const size_t step = 32768;  // (grid.y of the transform)
-        for (size_t p0 = 0; p0 < N; p0 += step) {
-            IrArgs a{};
-            a.H = H.p;
-            a.src = src + p0 * stride;
-            a.src_stride = (long long)stride;
-            a.len_data = (long long)len_data;
-            a.len_active = (long long)len_active;
-            a.tw = tw.p;
-            a.S = (int)S;
-            a.chan0 = (int)p0;
-            a.update_state = 0;
-            HIP_TRY(launch_ir_segments(log2b, a, (int)std::min(step, N - p0), s));
-        }
-        return FFTCONV_OK;
-    }
-
-    int zero_state(hipStream_t s) {  // :296-306
-        if (X.n) HIP_TRY(hipMemsetAsync(X.p, 0, X.bytes(), s));
-        if (ovl.n) HIP_TRY(hipMemsetAsync(ovl.p, 0, ovl.bytes(), s));
-        if (ib.n) HIP_TRY(hipMemsetAsync(ib.p, 0, ib.bytes(), s));
-        if (pre.n) HIP_TRY(hipMemsetAsync(pre.p, 0, pre.bytes(), s));
-        cur = 0;
-        fill = 0;
         return FFTCONV_OK;
     }
 
@@ -2543,209 +2530,48 @@ struct SparseMatrixCore {
         if (int r = alloc_geometry(dev, inputs, outputs, pairs, max_block, max_len)) return r;
         if (int r = zero_state(stream)) return r;
         if (int r = rebuild_plan(stream)) return r;
-        last_len = len;
-        if (S > 0) {
-            const bool shared = stride == 0 && N > 1;
-            if (len)
-                if (int r = hstage.upload(responses, shared ? 1 : N, len, stride, staging.p, ir_len, stream)) return r;
-            if (int r = ir_from_device(staging.p, shared ? 0 : ir_len, len, ir_len, stream)) return r;
-        }
-        HIP_TRY(hipStreamSynchronize(stream));
-        return FFTCONV_OK;
-    }
-
-    // FFTConvolver::update (:174-213) of every instance; (the caller has
-    // ordered s behind the handle's previous work)
-    int update_device(const float *src, size_t stride, size_t len, hipStream_t s) {
-        if (len > ir_len) return fail(FFTCONV_E_INVALID, "New impulse response is longer than initialized length");
-        if (ir_len == 0) return FFTCONV_OK;                         // :181-183
-        if (pre.n) HIP_TRY(hipMemsetAsync(pre.p, 0, pre.bytes(), s));   // :187
-        if (ovl.n) HIP_TRY(hipMemsetAsync(ovl.p, 0, ovl.bytes(), s));   // :188
-        act = ceil_div(len, B);                                     // :190 (current untouched)
-        last_len = len;
-        if (int r = rebuild_plan(s)) return r;
-        return ir_from_device(src, stride, len, len, s);
-    }
-    int update_host(const float *src, size_t len, size_t stride) {
-        if (len > ir_len) return fail(FFTCONV_E_INVALID, "New impulse response is longer than initialized length");
-        if (ir_len == 0) return FFTCONV_OK;
-        DeviceGuard g(device);
-        if (int r = order.enter(stream)) return r;
-        const bool shared = stride == 0 && N > 1;
-        if (len)
-            if (int r = hstage.upload(src, shared ? 1 : N, len, stride, staging.p, ir_len, stream)) return r;
-        return update_device(staging.p, shared ? 0 : ir_len, len, stream);
-    }
-
-    // One patch of H (matrix_patch.hip, generic in the pair index: here pair =
-    // the position in the pattern's list, H = [N][S][B]) from the lists staged
-    // in L's mirror, as MatrixCore::patch_device.
-    int patch_device(PairLists &L, size_t n_tr, size_t n_cp, const float2 *Hsrc, const float *src, size_t stride,
-                     bool by_pair, size_t len_data, size_t len_active, hipStream_t s) {
-        if (int r = L.push(n_tr, n_cp, s)) return r;
-        const size_t step = (size_t)kMatrixPatchChunk;
-        for (size_t c0 = 0; c0 < std::max(n_tr, n_cp); c0 += step) {
-            MatrixPatchArgs a{};
-            a.H = H.p;
-            a.Hsrc = Hsrc;
-            a.src = src;
-            a.src_stride = (long long)stride;
-            a.len_data = (long long)len_data;
-            a.len_active = (long long)len_active;
-            a.tw = tw.p;
-            a.tr = L.d.p + c0;
-            a.cp = L.d.p + L.cap + c0;
-            a.n_tr = (int)(c0 < n_tr ? std::min(step, n_tr - c0) : 0);
-            a.n_cp = (int)(c0 < n_cp ? std::min(step, n_cp - c0) : 0);
-            a.row0 = (int)c0;
-            a.by_pair = by_pair ? 1 : 0;
-            a.S = (int)S;
-            a.pairs = (int)N;
-            a.nt_cp = Variant::current().nt_matrix(H.bytes()) ? 1 : 0;
-            HIP_TRY(launch_matrix_patch(log2b, a, s));
-        }
-        return FFTCONV_OK;
-    }
-
-    // the pair list of an update_pairs call as positions in the pattern's list
-    int check_list(size_t n, const uint32_t *pair_out, const uint32_t *pair_in, uint32_t *idx) const {
-        if (n && (!pair_out || !pair_in)) return fail(FFTCONV_E_INVALID, "null pair list");
-        if (n > N) return fail(FFTCONV_E_INVALID, "the pair list must be strictly ascending in (output, input)");
-        size_t bad = 0;
-        const PairListError e = check_pairs_in_pattern(n, pair_out, pair_in, rowptr.data(), col.data(), I, O, idx, &bad);
-        if (e == PAIRS_ABSENT)
-            return fail(FFTCONV_E_INVALID, "pair (" + std::to_string(pair_out[bad]) + ", " + std::to_string(pair_in[bad]) +
-                                               ") is not in the pattern");
-        return e ? pair_list_error(e) : FFTCONV_OK;
-    }
-
-    // update(R'), R' = the responses this matrix holds with the n listed pairs
-    // (list positions, ascending, in L.tr()) replaced by rows 0..n-1 of src, at
-    // the length of the last init / update: update's side effects (the plan
-    // included), and only the listed pairs are transformed.
-    int update_pairs_device(PairLists &L, size_t n, const float *src, size_t stride, size_t len, hipStream_t s) {
-        if (len > last_len)
-            return fail(FFTCONV_E_INVALID, "update_pairs: response longer than the length the response set was applied at");
-        if (ir_len == 0) return FFTCONV_OK;
-        if (pre.n) HIP_TRY(hipMemsetAsync(pre.p, 0, pre.bytes(), s));
-        if (ovl.n) HIP_TRY(hipMemsetAsync(ovl.p, 0, ovl.bytes(), s));
-        act = ceil_div(last_len, B);
-        if (int r = rebuild_plan(s)) return r;
-        return patch_device(L, n, 0, nullptr, src, stride, false, len, last_len, s);
-    }
-    // the C ABI's two variants: d_src == false -- host rows through the pinned staging
-    int update_pairs(size_t n, const uint32_t *pair_out, const uint32_t *pair_in, const float *src, bool d_src,
-                     size_t len, size_t stride, hipStream_t s) {
-        if (int r = check_list(n, pair_out, pair_in, lists.idx.data())) return r;
-        if (len > last_len)
-            return fail(FFTCONV_E_INVALID, "update_pairs: response longer than the length the response set was applied at");
-        DeviceGuard g(device);
-        if (int r = order.enter(s)) return r;
-        if (int r = lists.acquire()) return r;
-        std::copy(lists.idx.begin(), lists.idx.begin() + n, lists.tr());
-        if (!d_src && len && n && ir_len) {
-            const bool shared = stride == 0 && n > 1;
-            if (int r = hstage.upload(src, shared ? 1 : n, len, stride, staging.p, ir_len, s)) return r;
-            return update_pairs_device(lists, n, staging.p, shared ? 0 : ir_len, len, s);
-        }
-        return update_pairs_device(lists, n, src, stride, len, s);
+        return init_responses(responses, len, stride);
     }
 
     int process_device(const float *din, size_t is, float *dout, size_t os, size_t n, hipStream_t s) {
-        if (n > (size_t)INT32_MAX) return fail(FFTCONV_E_UNSUPPORTED, "process length exceeds 2^31-1");
-        if (n == 0) return FFTCONV_OK;
-        if (act == 0) {  // :216-219 -- zero output, state untouched
-            HIP_TRY(hipMemset2DAsync(dout, os * sizeof(float), 0, n * sizeof(float), O, s));
-            return FFTCONV_OK;
-        }
+        bool launch;
+        if (int r = process_begin(dout, os, n, s, &launch); r || !launch) return r;
         MatrixSpArgs a{};
-        MatrixArgs &m = a.m;
-        m.H = H.p; m.X = X.p; m.ovl = ovl.p; m.ib = ib.p; m.pre = pre.p; m.part = part.p; m.tw = tw.p;
-        m.in_stride = (long long)is;
-        m.out_stride = (long long)os;
-        m.I = (int)I; m.O = (int)O; m.S = (int)S;
-        m.act = (int)act;
-        m.nt_h = Variant::current().nt_matrix(H.bytes()) ? 1 : 0;
+        call_args(a.m, is, os);
+        a.m.part = part.p;
         a.rowptr = d_rowptr.p; a.col = d_col.p; a.plan = plan.p; a.wg = wg.p;
-        a.N = (int)N;
+        a.N = (int)P;
         a.PT = (int)PT;
-        size_t processed = 0;
-        while (processed < n) {                                     // :222-294
-            const size_t k = std::min(n - processed, B - fill);     // :224-227
-            m.in = din + processed;
-            m.out = dout + processed;
-            m.cur = (int)cur;
-            m.fill = (int)fill;
-            m.k = (int)k;
+        for (size_t done = 0; done < n;) {                          // :222-294
+            const size_t k = chunk_args(a.m, din, dout, done, n);
             HIP_TRY(launch_matrix_sp_chunk(log2b, a, s));
-            fill += k;
-            if (fill == B) {                                        // :277-291
-                fill = 0;
-                cur = cur > 0 ? cur - 1 : act - 1;
-            }
-            processed += k;
+            advance(k, B);
+            done += k;
         }
         return FFTCONV_OK;
     }
 
-    int process_device_steps(const float *din, size_t is, size_t in_step, float *dout, size_t os, size_t out_step,
-                             size_t n, size_t steps, hipStream_t s) {
-        for (size_t k = 0; k < steps; ++k)
-            if (int r = process_device(din + k * in_step, is, dout + k * out_step, os, n, s)) return r;
-        return FFTCONV_OK;
+    // the fused crossfade launch (matrix_sp_xf.hip): what it takes beyond the
+    // shared arguments.  (In step, A and B have the same active_seg_count, so
+    // their plans are equal.)
+    void xf_args(XfArgs &x) const {
+        x.rowptr = d_rowptr.p; x.col = d_col.p; x.plan = plan.p; x.wg = wg.p;
+        x.N = (int)P;
+        x.PT = (int)PT;
     }
+    static hipError_t launch_xf_chunk(int log2b, const XfArgs &x, hipStream_t s) { return launch_matrix_sp_xf_chunk(log2b, x, s); }
 
-    int process_host(const float *in, size_t in_len, float *out, size_t out_len) {
-        if (in_len < out_len) return fail(FFTCONV_E_INVALID, "input slice shorter than output (range end index out of range)");
-        if (out_len == 0) return FFTCONV_OK;
-        DeviceGuard g(device);
-        if (int r = order.enter(stream)) return r;
-        if (int r = scratch.ensure(I * out_len, O * out_len)) return r;
-        HIP_TRY(hipMemcpy2DAsync(scratch.in.p, out_len * sizeof(float), in, in_len * sizeof(float),
-                                 out_len * sizeof(float), I, hipMemcpyHostToDevice, stream));
-        if (int r = process_device(scratch.in.p, out_len, scratch.out.p, out_len, out_len, stream)) return r;
-        HIP_TRY(hipMemcpyAsync(out, scratch.out.p, O * out_len * sizeof(float), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        return FFTCONV_OK;
-    }
-
-    // #[derive(Clone)]; `owner`: the clone is a SparseMatrixCrossfadeCore's
-    // convolver -- it runs on that stream and stages updates through its owner
-    int clone_from(const SparseMatrixCore &o, hipStream_t owner = nullptr) {
+    int clone_from(const SparseMatrixCore &o, hipStream_t owner = nullptr) {  // #[derive(Clone)]
         DeviceGuard g(o.device);
-        if (int r = o.order.drain(o.stream)) return r;
-        device = o.device;
-        I = o.I; O = o.O; N = o.N; ir_len = o.ir_len; B = o.B; log2b = o.log2b; S = o.S;
+        if (int r = clone_base(o, owner)) return r;
         PTmax = o.PTmax; PT = o.PT;
-        cur = o.cur; act = o.act; fill = o.fill; last_len = o.last_len;
         rowptr = o.rowptr;
         col = o.col;
-        if (owner) {
-            stream = owner;
-            own_stream = false;
-        } else {
-            HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-            if (int r = lists.alloc(N)) return r;
-        }
-        auto cp = [&](auto &dst, const auto &src) -> int {
-            if (int r = dst.alloc(src.n)) return r;
-            if (src.n) HIP_TRY(hipMemcpyAsync(dst.p, src.p, src.bytes(), hipMemcpyDeviceToDevice, stream));
-            return FFTCONV_OK;
-        };
-        if (int r = cp(H, o.H)) return r;
-        if (int r = cp(X, o.X)) return r;
-        if (int r = cp(pre, o.pre)) return r;
-        if (int r = cp(tw, o.tw)) return r;
-        if (int r = cp(ovl, o.ovl)) return r;
-        if (int r = cp(ib, o.ib)) return r;
-        if (int r = cp(d_rowptr, o.d_rowptr)) return r;
-        if (int r = cp(d_col, o.d_col)) return r;
-        if (int r = cp(plan, o.plan)) return r;
-        if (int r = cp(wg, o.wg)) return r;
-        if (int r = part.alloc(o.part.n)) return r;  // (rewritten by every block before it is read)
-        if (int r = staging.alloc(o.staging.n)) return r;
-        if (!owner)
-            if (int r = hstage.alloc(o.hstage.n, ir_len)) return r;
+        if (int r = clone_buffer(d_rowptr, o.d_rowptr, stream)) return r;
+        if (int r = clone_buffer(d_col, o.d_col, stream)) return r;
+        if (int r = clone_buffer(plan, o.plan, stream)) return r;
+        if (int r = clone_buffer(wg, o.wg, stream)) return r;
+        if (int r = clone_reserve(o)) return r;
         HIP_TRY(hipStreamSynchronize(stream));
         return FFTCONV_OK;
     }
@@ -2758,7 +2584,7 @@ struct SparseMatrixCore {
 // transforms and {current, active, fill}, as MatrixLookaheadCore's dense core
 // does; this core adds the near / far partial sums, its own plan (per output
 // the near and far part counts over its pair list, the far workgroups ordered
-// by anchor class) and the block count {t, tv} that schedules the anchors.
+// by anchor class) and the block clock that schedules the anchors.
 // (m.part, m.plan and m.wg are the plain sparse walk's and unused here.)
 // ---------------------------------------------------------------------------
 struct SparseMatrixLookaheadCore {
@@ -2771,17 +2597,15 @@ struct SparseMatrixLookaheadCore {
     size_t PnT = 0, PfT = 0;   // for the current active
     int coff[Q + 1] = {};      // the host's copy of the class offsets, from its copy of rowptr
     int class_outputs[Q] = {}; // outputs with at least one pair, per anchor class
-    long long t = 0, tv = 0;
-    bool windows = true;
+    LookaheadClock clk;
 
     int near_parts(size_t o) const { return matrix_sp_la_pn((long long)m.pairs_of(o), (int)m.act); }
     int far_parts(size_t o) const { return matrix_sp_la_pf((long long)m.pairs_of(o), (int)m.act); }
     // outputs with at least one pair that anchor when the next block starts
     int anchors() const {
-        if (!windows || m.act <= Q || m.cur >= m.act) return 0;
-        return class_outputs[(size_t)(t % (long long)Q)];
+        if (!clk.windows || m.act <= Q || m.cur >= m.act) return 0;
+        return class_outputs[(size_t)(clk.t % (long long)Q)];
     }
-    void invalidate() { tv = m.fill ? t + 1 : t; }
 
     // the sums the plan kernel computes, from the host's copy of the pattern
     void count(size_t active, size_t *pn, size_t *pf, int *offsets) const {
@@ -2832,7 +2656,7 @@ struct SparseMatrixLookaheadCore {
                                                    " outside 32..512 (use the SparseMatrixConvolver)");
         if (int r = m.init(dev, inputs, outputs, pairs, po, pi, responses, len, stride, max_block, max_len)) return r;
         DeviceGuard g(dev);
-        t = tv = 0;
+        clk = LookaheadClock();
         if (int r = alloc_extra()) return r;
         if (int r = rebuild_plan(m.stream)) return r;
         HIP_TRY(hipStreamSynchronize(m.stream));
@@ -2842,7 +2666,7 @@ struct SparseMatrixLookaheadCore {
         if (int r = m.update_device(src, stride, len, s)) return r;
         if (m.ir_len == 0) return FFTCONV_OK;
         if (int r = rebuild_plan(s)) return r;
-        invalidate();
+        clk.invalidate(m.fill);
         return FFTCONV_OK;
     }
     int update_host(const float *src, size_t len, size_t stride) {
@@ -2850,7 +2674,7 @@ struct SparseMatrixLookaheadCore {
         if (m.ir_len == 0) return FFTCONV_OK;
         DeviceGuard g(m.device);
         if (int r = rebuild_plan(m.stream)) return r;
-        invalidate();
+        clk.invalidate(m.fill);
         return FFTCONV_OK;
     }
     // update(R') of the sparse core at the held length: active and the plan stay;
@@ -2858,51 +2682,36 @@ struct SparseMatrixLookaheadCore {
     int update_pairs(size_t n, const uint32_t *pair_out, const uint32_t *pair_in, const float *src, bool d_src,
                      size_t len, size_t stride, hipStream_t s) {
         if (int r = m.update_pairs(n, pair_out, pair_in, src, d_src, len, stride, s)) return r;
-        invalidate();
+        clk.invalidate(m.fill);
         return FFTCONV_OK;
     }
     int reset(hipStream_t s) {
-        if (m.fill) ++t;  // (the block in progress is dropped: its number is not used again)
+        const size_t fill = m.fill;  // (zero_state clears it)
         if (int r = m.zero_state(s)) return r;
-        invalidate();
+        clk.reset(fill);
         return FFTCONV_OK;
     }
 
     int process_device(const float *din, size_t is, float *dout, size_t os, size_t n, hipStream_t s) {
-        if (n > (size_t)INT32_MAX) return fail(FFTCONV_E_UNSUPPORTED, "process length exceeds 2^31-1");
-        if (n == 0) return FFTCONV_OK;
-        if (m.act == 0) {  // :216-219 -- zero output, state untouched
-            HIP_TRY(hipMemset2DAsync(dout, os * sizeof(float), 0, n * sizeof(float), m.O, s));
-            return FFTCONV_OK;
-        }
+        bool launch;
+        if (int r = m.process_begin(dout, os, n, s, &launch); r || !launch) return r;
         MatrixSpLaArgs la{};
         MatrixArgs &a = la.m;
-        a.H = m.H.p; a.X = m.X.p; a.ovl = m.ovl.p; a.ib = m.ib.p; a.pre = m.pre.p; a.part = npart.p; a.tw = m.tw.p;
-        a.in_stride = (long long)is;
-        a.out_stride = (long long)os;
-        a.I = (int)m.I; a.O = (int)m.O; a.S = (int)m.S;
-        a.act = (int)m.act;
-        // by the whole H, as the dense lookahead matrix
-        a.nt_h = Variant::current().nt_matrix(m.H.bytes()) ? 1 : 0;
+        m.call_args(a, is, os);  // (nt_h by the whole H, as the dense lookahead matrix: DESIGN 4n)
+        a.part = npart.p;
         la.rowptr = m.d_rowptr.p; la.col = m.d_col.p;
         la.nplan = nplan.p; la.fplan = fplan.p; la.nwg = nwg.p; la.fwg = fwg.p;
         la.far = far.p;
-        la.N = (int)m.N;
+        la.N = (int)m.P;
         la.PnT = (int)PnT;
         la.PfT = (int)PfT;
-        size_t processed = 0;
-        while (processed < n) {                                     // :222-294
-            const size_t k = std::min(n - processed, m.B - m.fill); // :224-227
-            if (m.fill == 0 && (!windows || m.cur >= m.act)) tv = t + 1;  // no anchor in this block
-            a.in = din + processed;
-            a.out = dout + processed;
-            a.cur = (int)m.cur;
-            a.fill = (int)m.fill;
-            a.k = (int)k;
-            la.t = t;
-            la.tv = tv;
-            if (matrix_la_steady(t, tv)) {  // the anchoring class only
-                const size_t c = (size_t)(t % (long long)Q);
+        for (size_t done = 0; done < n;) {                          // :222-294
+            clk.begin_chunk(m.fill, m.cur, m.act);
+            const size_t k = m.chunk_args(a, din, dout, done, n);
+            la.t = clk.t;
+            la.tv = clk.tv;
+            if (matrix_la_steady(clk.t, clk.tv)) {  // the anchoring class only (the launcher checks by the same predicate)
+                const size_t c = (size_t)(clk.t % (long long)Q);
                 la.fbase = coff[c];
                 la.flen = coff[c + 1] - coff[c];
             } else {
@@ -2910,59 +2719,30 @@ struct SparseMatrixLookaheadCore {
                 la.flen = (int)PfT;
             }
             HIP_TRY(launch_matrix_sp_la_chunk(m.log2b, la, s));
-            m.fill += k;
-            if (m.fill == m.B) {                                    // :277-291
-                m.fill = 0;
-                m.cur = m.cur > 0 ? m.cur - 1 : m.act - 1;
-                ++t;
-            }
-            processed += k;
+            if (m.advance(k, m.B)) clk.block_done();
+            done += k;
         }
         return FFTCONV_OK;
     }
 
-    int process_device_steps(const float *din, size_t is, size_t in_step, float *dout, size_t os, size_t out_step,
-                             size_t n, size_t steps, hipStream_t s) {
-        for (size_t k = 0; k < steps; ++k)
-            if (int r = process_device(din + k * in_step, is, dout + k * out_step, os, n, s)) return r;
-        return FFTCONV_OK;
-    }
-
     int process_host(const float *in, size_t in_len, float *out, size_t out_len) {
-        if (in_len < out_len) return fail(FFTCONV_E_INVALID, "input slice shorter than output (range end index out of range)");
-        if (out_len == 0) return FFTCONV_OK;
-        DeviceGuard g(m.device);
-        if (int r = m.order.enter(m.stream)) return r;
-        if (int r = m.scratch.ensure(m.I * out_len, m.O * out_len)) return r;
-        HIP_TRY(hipMemcpy2DAsync(m.scratch.in.p, out_len * sizeof(float), in, in_len * sizeof(float),
-                                 out_len * sizeof(float), m.I, hipMemcpyHostToDevice, m.stream));
-        if (int r = process_device(m.scratch.in.p, out_len, m.scratch.out.p, out_len, out_len, m.stream)) return r;
-        HIP_TRY(hipMemcpyAsync(out, m.scratch.out.p, m.O * out_len * sizeof(float), hipMemcpyDeviceToHost, m.stream));
-        HIP_TRY(hipStreamSynchronize(m.stream));
-        return FFTCONV_OK;
+        return matrix_process_host(*this, m, in, in_len, out, out_len);
     }
 
-    int clone_from(const SparseMatrixLookaheadCore &o) {  // #[derive(Clone)]: the windows, the plans and {t, tv} too
+    int clone_from(const SparseMatrixLookaheadCore &o) {  // #[derive(Clone)]: the windows, the plans and the clock too
         if (int r = m.clone_from(o.m)) return r;
         DeviceGuard g(m.device);
-        t = o.t;
-        tv = o.tv;
-        windows = o.windows;
+        clk = o.clk;
         PnT = o.PnT;
         PfT = o.PfT;
         std::copy(o.coff, o.coff + Q + 1, coff);
         std::copy(o.class_outputs, o.class_outputs + Q, class_outputs);
-        auto cp = [&](auto &dst, const auto &src) -> int {
-            if (int r = dst.alloc(src.n)) return r;
-            if (src.n) HIP_TRY(hipMemcpyAsync(dst.p, src.p, src.bytes(), hipMemcpyDeviceToDevice, m.stream));
-            return FFTCONV_OK;
-        };
-        if (int r = cp(far, o.far)) return r;
-        if (int r = cp(nplan, o.nplan)) return r;
-        if (int r = cp(fplan, o.fplan)) return r;
-        if (int r = cp(d_coff, o.d_coff)) return r;
-        if (int r = cp(nwg, o.nwg)) return r;
-        if (int r = cp(fwg, o.fwg)) return r;
+        if (int r = clone_buffer(far, o.far, m.stream)) return r;
+        if (int r = clone_buffer(nplan, o.nplan, m.stream)) return r;
+        if (int r = clone_buffer(fplan, o.fplan, m.stream)) return r;
+        if (int r = clone_buffer(d_coff, o.d_coff, m.stream)) return r;
+        if (int r = clone_buffer(nwg, o.nwg, m.stream)) return r;
+        if (int r = clone_buffer(fwg, o.fwg, m.stream)) return r;
         if (int r = npart.alloc(o.npart.n)) return r;  // (rewritten by every block before it is read)
         HIP_TRY(hipStreamSynchronize(m.stream));
         return FFTCONV_OK;
@@ -2970,34 +2750,42 @@ struct SparseMatrixLookaheadCore {
 };
 
 // ---------------------------------------------------------------------------
-// MatrixCrossfadeCore -- I x O CrossfadeConvolver<FFTConvolver> instances
-// (o, i) in lockstep: two MatrixCores A and B on the handle's
-// stream, ONE Crossfader and one response_pending for all of them, the mix
-// applied to the per-output sums.
+// MatrixCrossfadeCoreT -- P CrossfadeConvolver<FFTConvolver> instances in
+// lockstep, one per pair of a dense or a sparse (§4p) matrix: two
+// Conv cores A and B on the handle's stream, ONE Crossfader and one
+// response_pending for all of them, the mix applied to the per-output sums.
+// "Pair" is Conv's pair index throughout (the PairBook, the lists, the stored
+// response [P][stored_len]).
 //   composition path: A.process_device -> buf_a, B.process_device -> buf_b,
 //       crossfade_mix_kernel over the O outputs (always correct)
-//   fused path (matrix_xf.hip), while A and B are in step: one R2C per input
-//       for both delay lines, the live convolvers' MAC from one X stream, the
-//       finish of each live convolver and the mix in one launch.  A convolver
-//       the crossfader has Reached away from is idle: its output is never
-//       observed and the next thing that happens to it is update(), which
-//       zeroes its pre_multiplied and overlap (src/fft_convolver.rs:186-188),
-//       so it carries only its delay line and input buffer forward.
+//   fused path (matrix_xf.hip / matrix_sp_xf.hip), while A and B are in step:
+//       one R2C per input for both delay lines, the live convolvers' MAC from
+//       one X stream, the finish of each live convolver and the mix in one
+//       launch.  A convolver the crossfader has Reached away from is idle: its
+//       output is never observed and the next thing that happens to it is
+//       update(), which zeroes its pre_multiplied and overlap
+//       (src/fft_convolver.rs:186-188), so it carries only its delay line and
+//       input buffer forward.
+// Conv supplies kName, check_list, rebuild_plan (a swap that changes the target
+// convolver's active_seg_count rebuilds what depends on it before that
+// convolver's next launch), and the fused launch: XfArgs, xf_args,
+// launch_xf_chunk.
 // ---------------------------------------------------------------------------
-struct MatrixCrossfadeCore {
+template <class Conv>
+struct MatrixCrossfadeCoreT {
     int device = 0;
-    size_t I = 0, O = 0, max_buffer_size = 0, stored_len = 0, stored_stride = 0;
+    size_t I = 0, O = 0, P = 0, max_buffer_size = 0, stored_len = 0, stored_stride = 0;
     size_t stage_row = 0;  // hstage row: the stored response, or a direct update of a / b
-    std::unique_ptr<MatrixCore> a, b;
+    std::unique_ptr<Conv> a, b;
     Crossfader xf;
-    DevPtr<float> buf_a, buf_b, stored;  // stored [O*I][stored_len]
+    DevPtr<float> buf_a, buf_b, stored;  // stored [P][stored_len]
     DevPtr<float> mix_tab;               // [max_buffer_size + 1] mix_value walk of one call
     bool response_pending = false;
     // A and B have had equal {current, active, fill} and active > 0 at every
     // call since creation: their delay lines and input buffers are equal row
     // for row.  Sticky off (an update to another ceil(len / B) ends it for good).
     bool in_step = false;
-    bool fused = true;  // fftconv_matrix_crossfade_set_fused
+    bool fused = true;  // fftconv_matrix[_sparse]_crossfade_set_fused
     // a launch failed between the two convolvers' work: they may be out of
     // step with the host's state.  Every later call fails.
     bool poisoned = false;
@@ -3011,12 +2799,12 @@ struct MatrixCrossfadeCore {
     PairLists lists;
 
     int check_poisoned() const {
-        return poisoned ? fail(FFTCONV_E_DEVICE, "matrix crossfade handle unusable: an earlier process() failed "
-                                                  "between its two convolvers' launches")
+        return poisoned ? fail(FFTCONV_E_DEVICE, std::string(Conv::kName) + " crossfade handle unusable: an earlier process() "
+                                                                            "failed between its two convolvers' launches")
                         : FFTCONV_OK;
     }
 
-    ~MatrixCrossfadeCore() {
+    ~MatrixCrossfadeCoreT() {
         if (stream) {
             DeviceGuard g(device);
             (void)order.drain(stream);
@@ -3028,442 +2816,44 @@ struct MatrixCrossfadeCore {
     bool states_agree() const {
         return a->cur == b->cur && a->act == b->act && a->fill == b->fill && a->act > 0;
     }
+    // the convolver that is not the crossfader's target, and the target
+    Conv &other_conv() const { return xf.target == 0 ? *b : *a; }
+    Conv &target_conv() const { return xf.target == 0 ? *a : *b; }
 
     int alloc_buffers(size_t hstage_count) {
-        if (int r = stored.alloc(O * I * stored_len)) return r;
+        if (int r = stored.alloc(P * stored_len)) return r;
         if (int r = hstage.alloc(hstage_count, stage_row)) return r;
         if (int r = buf_a.alloc(O * max_buffer_size)) return r;
         if (int r = buf_b.alloc(O * max_buffer_size)) return r;
-        if (int r = lists.alloc(O * I)) return r;
-        book.init(O * I);
+        if (int r = lists.alloc(P)) return r;
+        book.init(P);
         return mix_tab.alloc(max_buffer_size + 1);
+    }
+    // A and B as clones of the two convolvers ca and cb, on this handle's new stream
+    int clone_convolvers(const Conv &ca, const Conv &cb) {
+        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        a.reset(new (std::nothrow) Conv());
+        b.reset(new (std::nothrow) Conv());
+        if (!a || !b) return fail(FFTCONV_E_NOMEM, "out of host memory");
+        if (int r = a->clone_from(ca, stream)) return r;
+        return b->clone_from(cb, stream);
     }
 
     // CrossfadeConvolver::new (:19-43)
-    int init_new(const MatrixCore &conv, size_t max_response_length, size_t mbs, size_t crossfade_samples) {
+    int init_new(const Conv &conv, size_t max_response_length, size_t mbs, size_t crossfade_samples) {
         if (mbs > (size_t)INT32_MAX) return fail(FFTCONV_E_UNSUPPORTED, "max_buffer_size exceeds 2^31-1");
         device = conv.device;
         I = conv.I;
         O = conv.O;
+        P = conv.P;
         DeviceGuard g(device);
-        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        a.reset(new (std::nothrow) MatrixCore());
-        b.reset(new (std::nothrow) MatrixCore());
-        if (!a || !b) return fail(FFTCONV_E_NOMEM, "out of host memory");
-        if (int r = a->clone_from(conv, stream)) return r;
-        if (int r = b->clone_from(conv, stream)) return r;
+        if (int r = clone_convolvers(conv, conv)) return r;
         in_step = states_agree();
         stored_len = max_response_length;
         stored_stride = stored_len;
         stage_row = std::max(stored_len, a->ir_len);
         max_buffer_size = mbs;
-        if (int r = alloc_buffers(O * I * stage_row)) return r;
-        if (stored.n) HIP_TRY(hipMemsetAsync(stored.p, 0, stored.bytes(), stream));
-        xf.init(crossfade_samples, std::min(mbs, max_response_length));
-        HIP_TRY(hipStreamSynchronize(stream));
-        return FFTCONV_OK;
-    }
-
-    int quiesce() const { return order.drain(stream); }
-    bool is_crossfading() const { return xf.approaching; }  // :85-92
-
-    // swap (:94-105) from device samples: update the convolver that is not the
-    // target, then fade into it
-    int swap_device(const float *src, size_t stride, size_t len, hipStream_t s) {
-        const int to = xf.target == 0 ? 1 : 0;
-        if (int r = (to ? *b : *a).update_device(src, stride, len, s)) return r;
-        xf.fade_into(to);
-        book.whole_applied();  // every pair of A and B may differ now
-        return FFTCONV_OK;
-    }
-
-    // The partial swap: update(R') of the convolver T that is not
-    // the target, R' = the target's responses with the n listed pairs (`lst`,
-    // ascending) replaced at len_active samples, then the fade into T.  T's
-    // spectra differ from the target's in the pairs of D only, so the pairs of
-    // D minus lst are copied from the target's spectra, the listed ones are
-    // transformed from `src` (entry k reads row k, or -- by_pair -- row lst[k]),
-    // and D = lst.  One launch; no allocation, no host wait beyond the lists'
-    // mirror.
-    int swap_pairs_device(const uint32_t *lst, size_t n, const float *src, size_t stride, bool by_pair,
-                          size_t len_data, size_t len_active, hipStream_t s) {
-        const int to = xf.target == 0 ? 1 : 0;
-        MatrixCore &t = to ? *b : *a, &other = to ? *a : *b;
-        if (len_active > t.ir_len) return fail(FFTCONV_E_INVALID, "New impulse response is longer than initialized length");
-        if (int r = lists.acquire()) return r;
-        if (n) std::copy(lst, lst + n, lists.tr());
-        const size_t n_cp = book.partial_applied(lst, n, lists.cp());
-        if (t.ir_len != 0) {
-            if (t.pre.n) HIP_TRY(hipMemsetAsync(t.pre.p, 0, t.pre.bytes(), s));   // update's side effects (:186-190)
-            if (t.ovl.n) HIP_TRY(hipMemsetAsync(t.ovl.p, 0, t.ovl.bytes(), s));
-            t.act = ceil_div(len_active, t.B);
-            t.last_len = len_active;
-            if (int r = t.patch_device(lists, n, n_cp, other.H.p, src, stride, by_pair, len_data, len_active, s)) return r;
-        }
-        xf.fade_into(to);
-        return FFTCONV_OK;
-    }
-
-    // the pending response, whole or partial, into the convolver that is not the target
-    int apply_pending(hipStream_t s) {
-        if (!book.partial) return swap_device(stored.p, stored_stride, stored_len, s);
-        const size_t n = book.pending_list(lists.idx.data());
-        if (int r = swap_pairs_device(lists.idx.data(), n, stored.p, stored_len, true, stored_len, stored_len, s)) return r;
-        book.clear_pending();
-        return FFTCONV_OK;
-    }
-
-    // rows k of a listed update (`len` samples each, on the host or the device)
-    // to the stored response's rows lst[k], zero-padded to stored_len
-    int store_rows(const uint32_t *lst, size_t n, const float *src, bool d_src, size_t len, size_t stride, hipStream_t s) {
-        for (size_t k0 = 0; k0 < n;) {
-            size_t k1 = k0 + 1;
-            while (k1 < n && lst[k1] == lst[k1 - 1] + 1) ++k1;
-            float *dst = stored.p + (size_t)lst[k0] * stored_len;
-            if (len < stored_len) HIP_TRY(hipMemsetAsync(dst, 0, (k1 - k0) * stored_len * sizeof(float), s));
-            if (len && d_src) {
-                if (stride >= len) {
-                    HIP_TRY(hipMemcpy2DAsync(dst, stored_len * sizeof(float), src + k0 * stride, stride * sizeof(float),
-                                             len * sizeof(float), k1 - k0, hipMemcpyDeviceToDevice, s));
-                } else {  // (stride 0: one response for every listed pair)
-                    for (size_t k = k0; k < k1; ++k)
-                        HIP_TRY(hipMemcpyAsync(dst + (k - k0) * stored_len, src + k * stride, len * sizeof(float),
-                                               hipMemcpyDeviceToDevice, s));
-                }
-            }
-            k0 = k1;
-        }
-        if (len && !d_src) return hstage.upload_scatter(src, n, len, stride, stored.p, stored_len, lst, s);
-        return FFTCONV_OK;
-    }
-
-    // update_pairs: update(R'), R' = the base set with the listed pairs replaced
-    // (DESIGN §4o).  `s` is ordered behind the handle's previous work.
-    int update_pairs(size_t n, const uint32_t *pair_out, const uint32_t *pair_in, const float *src, bool d_src,
-                     size_t len, size_t stride, hipStream_t s) {
-        if (int r = check_poisoned()) return r;
-        if (n && (!pair_out || !pair_in)) return fail(FFTCONV_E_INVALID, "null pair list");
-        if (n > O * I) return fail(FFTCONV_E_INVALID, "the pair list must be strictly ascending in (output, input)");
-        uint32_t *lst = lists.idx.data();
-        if (PairListError e = check_pairs(n, pair_out, pair_in, I, O, lst)) return pair_list_error(e);
-        MatrixCore &t = xf.target == 0 ? *b : *a, &base = xf.target == 0 ? *a : *b;
-        const bool fading = is_crossfading();
-        DeviceGuard g(device);
-        if (!fading && !response_pending) {
-            // the base set is the target convolver's, at the length it was applied at
-            const size_t lenp = base.last_len;
-            if (len > lenp)
-                return fail(FFTCONV_E_INVALID, "update_pairs: response longer than the length the response set was applied at");
-            if (int r = order.enter(s)) return r;
-            if (!d_src && len && n && t.ir_len) {
-                const bool shared = stride == 0 && n > 1;
-                if (int r = hstage.upload(src, shared ? 1 : n, len, stride, t.staging.p, t.ir_len, s)) return r;
-                return swap_pairs_device(lst, n, t.staging.p, shared ? 0 : t.ir_len, false, len, lenp, s);
-            }
-            return swap_pairs_device(lst, n, src, stride, false, len, lenp, s);
-        }
-        // the base set is, or becomes, a stored response of stored_len samples
-        if (len > stored_len)
-            return fail(FFTCONV_E_INVALID, fading ? "assertion failed: response_len <= self.stored_response.len()"
-                                                  : "update_pairs: response longer than the stored response");
-        const bool whole = response_pending && !book.partial;
-        if (!whole && ceil_div(stored_len, base.B) != base.act)
-            return fail(FFTCONV_E_UNSUPPORTED, "update_pairs during a fade: the stored length gives another active segment "
-                                               "count than the base convolver's, so zero-padding cannot reproduce update()");
-        if (!fading && stored_len > t.ir_len)
-            return fail(FFTCONV_E_INVALID, "New impulse response is longer than initialized length");
-        if (int r = order.enter(s)) return r;
-        if (whole && stored_stride == 0 && O * I > 1) {
-            // a shared stored response: every pair gets its own row first
-            for (size_t k = 1; k < O * I; k *= 2)
-                HIP_TRY(hipMemcpyAsync(stored.p + k * stored_len, stored.p, std::min(k, O * I - k) * stored_len * sizeof(float),
-                                       hipMemcpyDeviceToDevice, s));
-            stored_stride = stored_len;
-        }
-        if (int r = store_rows(lst, n, src, d_src, len, stride, s)) return r;
-        if (!whole) {
-            book.merge_pending(lst, n);  // (a pair listed twice: the later rows have replaced the earlier ones)
-            stored_stride = stored_len;
-        }
-        response_pending = true;
-        if (!fading) {  // the fade has ended: update(R') swaps at once
-            if (int r = apply_pending(s)) return r;
-            response_pending = false;
-        }
-        return FFTCONV_OK;
-    }
-
-    // Convolution::update (:51-64) from host samples (pair p at src + p * stride,
-    // stride 0 = one response for every pair); staged in pinned memory and
-    // enqueued behind the handle's work: no allocation, no host wait
-    int update_host(const float *src, size_t len, size_t stride) {
-        if (int r = check_poisoned()) return r;
-        DeviceGuard g(device);
-        const bool shared = stride == 0 && O * I > 1;
-        const size_t rows = shared ? 1 : O * I;
-        if (!is_crossfading()) {
-            MatrixCore &t = xf.target == 0 ? *b : *a;
-            if (len > t.ir_len) return fail(FFTCONV_E_INVALID, "New impulse response is longer than initialized length");
-            if (int r = order.enter(stream)) return r;
-            if (len)
-                if (int r = hstage.upload(src, rows, len, stride, t.staging.p, t.ir_len, stream)) return r;
-            if (int r = swap_device(t.staging.p, shared ? 0 : t.ir_len, len, stream)) return r;
-            response_pending = false;
-            book.clear_pending();
-            return FFTCONV_OK;
-        }
-        if (len > stored_len) return fail(FFTCONV_E_INVALID, "assertion failed: response_len <= self.stored_response.len()");
-        if (int r = order.enter(stream)) return r;
-        // stored_response[..len] = response; stored_response[len..] = 0
-        if (stored.n) HIP_TRY(hipMemsetAsync(stored.p, 0, stored.bytes(), stream));
-        if (len)
-            if (int r = hstage.upload(src, rows, len, stride, stored.p, stored_len, stream)) return r;
-        stored_stride = shared ? 0 : stored_len;
-        response_pending = true;
-        book.clear_pending();  // (a whole response replaces a pending partial one)
-        return FFTCONV_OK;
-    }
-
-    // Convolution::update (:51-64) from device samples, stream-ordered (the
-    // caller has ordered s behind the handle's previous work)
-    int update_device(const float *src, size_t len, size_t stride, hipStream_t s) {
-        if (int r = check_poisoned()) return r;
-        if (!is_crossfading()) {
-            if (int r = swap_device(src, stride, len, s)) return r;
-            response_pending = false;
-            book.clear_pending();
-            return FFTCONV_OK;
-        }
-        if (len > stored_len) return fail(FFTCONV_E_INVALID, "assertion failed: response_len <= self.stored_response.len()");
-        const bool shared = stride == 0 && O * I > 1;
-        if (stored.n) HIP_TRY(hipMemsetAsync(stored.p, 0, stored.bytes(), s));
-        if (len)
-            HIP_TRY(hipMemcpy2DAsync(stored.p, stored_len * sizeof(float), src, (shared ? len : std::max(stride, len)) * sizeof(float),
-                                     len * sizeof(float), shared ? 1 : O * I, hipMemcpyDeviceToDevice, s));
-        stored_stride = shared ? 0 : stored_len;
-        response_pending = true;
-        book.clear_pending();  // (a whole response replaces a pending partial one)
-        return FFTCONV_OK;
-    }
-
-    CrossfadeMixArgs mix_args(float *dout, size_t os, size_t out_len) const {
-        CrossfadeMixArgs x{};
-        x.buf_a = buf_a.p; x.buf_b = buf_b.p; x.buf_stride = (long long)max_buffer_size;
-        x.out = dout; x.out_stride = (long long)os; x.n = (int)out_len;
-        x.approaching = xf.approaching ? 1 : 0; x.target = xf.target;
-        x.counter0 = xf.counter; x.fading = xf.fading_samples;
-        x.mix_value0 = xf.mix_value; x.step = xf.mix_value_step;
-        return x;
-    }
-
-    // 0 = composition, 1 = fused with both convolvers live, 2 = fused with one
-    // idle: a function of the handle's state only
-    int path_now() const {
-        if (!fused || !in_step || !states_agree()) return 0;
-        return xf.approaching ? 1 : 2;
-    }
-    // the path the next process() takes: a pending swap is applied first
-    int path_next() const {
-        if (!is_crossfading() && response_pending) {
-            const MatrixCore &t = xf.target == 0 ? *b : *a, &other = xf.target == 0 ? *a : *b;
-            if (t.ir_len == 0 || stored_len > t.ir_len) return path_now();  // (the update changes nothing)
-            const size_t act = ceil_div(stored_len, t.B);
-            return fused && in_step && act > 0 && act == other.act && t.cur == other.cur && t.fill == other.fill ? 1 : 0;
-        }
-        return path_now();
-    }
-
-    // Convolution::process (:66-78): both convolvers advance by max_buffer_size
-    // samples, the first out_len mixed samples are written
-    int process_device(const float *din, size_t is, float *dout, size_t os, size_t out_len, hipStream_t s) {
-        if (int r = check_poisoned()) return r;
-        if (out_len > max_buffer_size) return fail(FFTCONV_E_INVALID, "output longer than max_buffer_size (index out of bounds)");
-        if (!is_crossfading() && response_pending) {                    // :67-70
-            if (int r = apply_pending(s)) return r;
-            response_pending = false;
-        }
-        const size_t m = max_buffer_size;
-        if (m == 0) return FFTCONV_OK;
-        in_step = in_step && states_agree();
-        CrossfadeMixArgs mx = mix_args(dout, os, out_len);
-        if (path_now() == 0) {
-            if (int r = a->process_device(din, is, buf_a.p, m, m, s)) return r;    // :72
-            if (int r = b->process_device(din, is, buf_b.p, m, m, s)) {            // :73
-                poisoned = true;
-                return r;
-            }
-            if (out_len > 1024 && mx.approaching) {
-                HIP_TRY(launch_crossfade_walk(mx, mix_tab.p, s));
-                mx.vtab = mix_tab.p;
-            }
-            HIP_TRY(launch_crossfade_mix(mx, (int)O, s));                          // :75-77
-            xf.advance(out_len);
-            return FFTCONV_OK;
-        }
-        if (mx.approaching) mx.vtab = mix_tab.p;  // the call's mix_value walk: launch A of the first chunk fills it
-        MatrixXfArgs x{};
-        const MatrixCore *cv[2] = {a.get(), b.get()};
-        for (int c = 0; c < 2; ++c) {
-            x.H[c] = cv[c]->H.p; x.X[c] = cv[c]->X.p; x.ovl[c] = cv[c]->ovl.p; x.ib[c] = cv[c]->ib.p;
-            x.pre[c] = cv[c]->pre.p; x.part[c] = cv[c]->part.p;
-        }
-        x.tw = a->tw.p;
-        x.in_stride = (long long)is;
-        x.out_stride = (long long)os;
-        x.I = (int)I; x.O = (int)O; x.S = (int)a->S;
-        x.P = a->mac_parts();
-        x.rpp = (int)ceil_div(I * (a->act - 1), (size_t)x.P);
-        x.act = (int)a->act;
-        x.nt_h = Variant::current().nt_matrix(a->H.bytes()) ? 1 : 0;
-        x.live = xf.approaching ? 3 : (xf.target == 0 ? 1 : 2);
-        x.mix = mx;
-        const size_t B = a->B;
-        size_t processed = 0;
-        while (processed < m) {                                         // FFTConvolver::process :222-294, A and B at once
-            const size_t k = std::min(m - processed, B - a->fill);
-            x.in = din + processed;
-            x.out = dout + processed;
-            x.cur = (int)a->cur;
-            x.fill = (int)a->fill;
-            x.k = (int)k;
-            x.off = (int)processed;
-            x.walk = processed == 0 && mx.approaching ? mix_tab.p : nullptr;
-            if (hipError_t e = launch_matrix_xf_chunk(a->log2b, x, s); e != hipSuccess) {
-                poisoned = true;
-                HIP_TRY(e);
-            }
-            a->fill += k;
-            if (a->fill == B) {
-                a->fill = 0;
-                a->cur = a->cur > 0 ? a->cur - 1 : a->act - 1;
-            }
-            b->fill = a->fill;
-            b->cur = a->cur;
-            processed += k;
-        }
-        xf.advance(out_len);
-        return FFTCONV_OK;
-    }
-
-    int process_host(const float *in, size_t in_len, float *out, size_t out_len) {
-        if (in_len < max_buffer_size) return fail(FFTCONV_E_INVALID, "input shorter than max_buffer_size (range end index out of range)");
-        if (out_len > max_buffer_size) return fail(FFTCONV_E_INVALID, "output longer than max_buffer_size (index out of bounds)");
-        if (int r = check_poisoned()) return r;
-        DeviceGuard g(device);
-        if (int r = order.enter(stream)) return r;
-        const size_t m = max_buffer_size, on = std::max<size_t>(out_len, 1);
-        if (int r = scratch.ensure(I * std::max<size_t>(m, 1), O * on)) return r;
-        if (m)
-            HIP_TRY(hipMemcpy2DAsync(scratch.in.p, m * sizeof(float), in, in_len * sizeof(float), m * sizeof(float), I,
-                                     hipMemcpyHostToDevice, stream));
-        if (int r = process_device(scratch.in.p, m, scratch.out.p, on, out_len, stream)) return r;
-        if (out_len && m)
-            HIP_TRY(hipMemcpy2DAsync(out, out_len * sizeof(float), scratch.out.p, on * sizeof(float),
-                                     out_len * sizeof(float), O, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        return FFTCONV_OK;
-    }
-
-    int clone_from(const MatrixCrossfadeCore &o) {
-        DeviceGuard g(o.device);
-        if (int r = o.order.drain(o.stream)) return r;
-        device = o.device; I = o.I; O = o.O; max_buffer_size = o.max_buffer_size;
-        stored_len = o.stored_len; stored_stride = o.stored_stride; stage_row = o.stage_row;
-        xf = o.xf; response_pending = o.response_pending;
-        in_step = o.in_step; fused = o.fused; poisoned = o.poisoned;
-        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        a.reset(new (std::nothrow) MatrixCore());
-        b.reset(new (std::nothrow) MatrixCore());
-        if (!a || !b) return fail(FFTCONV_E_NOMEM, "out of host memory");
-        if (int r = a->clone_from(*o.a, stream)) return r;
-        if (int r = b->clone_from(*o.b, stream)) return r;
-        if (int r = alloc_buffers(o.hstage.n)) return r;
-        book.copy_from(o.book);
-        if (stored.n) HIP_TRY(hipMemcpyAsync(stored.p, o.stored.p, stored.bytes(), hipMemcpyDeviceToDevice, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        return FFTCONV_OK;
-    }
-};
-
-// ---------------------------------------------------------------------------
-// SparseMatrixCrossfadeCore -- N CrossfadeConvolver<FFTConvolver> instances in
-// lockstep, one per listed pair: MatrixCrossfadeCore over two
-// SparseMatrixCores A and B on the handle's stream -- one Crossfader, one
-// response_pending, the mix applied to the per-output sums, the same three
-// paths.  "Pair" is a position in the pattern's list throughout (the PairBook,
-// the lists, the stored response [N][stored_len]).  A copy of the dense core
-// kept honest by the bitwise tests against it; the one difference: a swap that
-// changes the target convolver's active_seg_count rebuilds that convolver's
-// plan on the stream before its next launch.
-// ---------------------------------------------------------------------------
-struct SparseMatrixCrossfadeCore {
-    int device = 0;
-    size_t I = 0, O = 0, N = 0, max_buffer_size = 0, stored_len = 0, stored_stride = 0;
-    size_t stage_row = 0;  // hstage row: the stored response, or a direct update of a / b
-    std::unique_ptr<SparseMatrixCore> a, b;
-    Crossfader xf;
-    DevPtr<float> buf_a, buf_b, stored;  // stored [N][stored_len]
-    DevPtr<float> mix_tab;               // [max_buffer_size + 1] mix_value walk of one call
-    bool response_pending = false;
-    bool in_step = false;  // as MatrixCrossfadeCore: sticky off
-    bool fused = true;     // fftconv_matrix_sparse_crossfade_set_fused
-    bool poisoned = false; // a launch failed between the two convolvers' work
-    hipStream_t stream = nullptr;
-    Scratch scratch;
-    mutable StreamOrder order;
-    PinnedStage hstage;
-    PairBook book;
-    PairLists lists;
-
-    int check_poisoned() const {
-        return poisoned ? fail(FFTCONV_E_DEVICE, "sparse matrix crossfade handle unusable: an earlier process() failed "
-                                                  "between its two convolvers' launches")
-                        : FFTCONV_OK;
-    }
-
-    ~SparseMatrixCrossfadeCore() {
-        if (stream) {
-            DeviceGuard g(device);
-            (void)order.drain(stream);
-            a.reset(); b.reset();  // (they borrow `stream`)
-            (void)hipStreamDestroy(stream);
-        }
-    }
-
-    bool states_agree() const {
-        return a->cur == b->cur && a->act == b->act && a->fill == b->fill && a->act > 0;
-    }
-
-    int alloc_buffers(size_t hstage_count) {
-        if (int r = stored.alloc(N * stored_len)) return r;
-        if (int r = hstage.alloc(hstage_count, stage_row)) return r;
-        if (int r = buf_a.alloc(O * max_buffer_size)) return r;
-        if (int r = buf_b.alloc(O * max_buffer_size)) return r;
-        if (int r = lists.alloc(N)) return r;
-        book.init(N);
-        return mix_tab.alloc(max_buffer_size + 1);
-    }
-
-    // CrossfadeConvolver::new (:19-43)
-    int init_new(const SparseMatrixCore &conv, size_t max_response_length, size_t mbs, size_t crossfade_samples) {
-        if (mbs > (size_t)INT32_MAX) return fail(FFTCONV_E_UNSUPPORTED, "max_buffer_size exceeds 2^31-1");
-        device = conv.device;
-        I = conv.I;
-        O = conv.O;
-        N = conv.N;
-        DeviceGuard g(device);
-        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        a.reset(new (std::nothrow) SparseMatrixCore());
-        b.reset(new (std::nothrow) SparseMatrixCore());
-        if (!a || !b) return fail(FFTCONV_E_NOMEM, "out of host memory");
-        if (int r = a->clone_from(conv, stream)) return r;
-        if (int r = b->clone_from(conv, stream)) return r;
-        in_step = states_agree();
-        stored_len = max_response_length;
-        stored_stride = stored_len;
-        stage_row = std::max(stored_len, a->ir_len);
-        max_buffer_size = mbs;
-        if (int r = alloc_buffers(N * stage_row)) return r;
+        if (int r = alloc_buffers(P * stage_row)) return r;
         if (stored.n) HIP_TRY(hipMemsetAsync(stored.p, 0, stored.bytes(), stream));
         xf.init(crossfade_samples, std::min(mbs, max_response_length));
         HIP_TRY(hipStreamSynchronize(stream));
@@ -3477,33 +2867,36 @@ struct SparseMatrixCrossfadeCore {
     // target (its plan included), then fade into it
     int swap_device(const float *src, size_t stride, size_t len, hipStream_t s) {
         const int to = xf.target == 0 ? 1 : 0;
-        if (int r = (to ? *b : *a).update_device(src, stride, len, s)) return r;
+        if (int r = other_conv().update_device(src, stride, len, s)) return r;
         xf.fade_into(to);
         book.whole_applied();  // every pair of A and B may differ now
         return FFTCONV_OK;
     }
 
-    // The partial swap, as MatrixCrossfadeCore::swap_pairs_device: update(R') of
-    // the convolver T that is not the target.  T's active_seg_count becomes
-    // ceil(len_active / B), so its plan is rebuilt behind the stream's earlier
-    // launches and ahead of T's next one.
+    // The partial swap: update(R') of the convolver T that is
+    // not the target, R' = the target's responses with the n listed pairs
+    // (`lst`, ascending) replaced at len_active samples, then the fade into T.
+    // T's spectra differ from the target's in the pairs of D only, so the pairs
+    // of D minus lst are copied from the target's spectra, the listed ones are
+    // transformed from `src` (entry k reads row k, or -- by_pair -- row lst[k]),
+    // and D = lst.  T's active_seg_count becomes ceil(len_active / B); where
+    // that changes it, T's plan is rebuilt behind the stream's earlier launches
+    // and ahead of T's next one.  One patch launch; no allocation, no host wait
+    // beyond the lists' mirror.
     int swap_pairs_device(const uint32_t *lst, size_t n, const float *src, size_t stride, bool by_pair,
                           size_t len_data, size_t len_active, hipStream_t s) {
         const int to = xf.target == 0 ? 1 : 0;
-        SparseMatrixCore &t = to ? *b : *a, &other = to ? *a : *b;
+        Conv &t = other_conv(), &other = target_conv();
         if (len_active > t.ir_len) return fail(FFTCONV_E_INVALID, "New impulse response is longer than initialized length");
         if (int r = lists.acquire()) return r;
         if (n) std::copy(lst, lst + n, lists.tr());
         const size_t n_cp = book.partial_applied(lst, n, lists.cp());
         if (t.ir_len != 0) {
-            if (t.pre.n) HIP_TRY(hipMemsetAsync(t.pre.p, 0, t.pre.bytes(), s));   // update's side effects (:186-190)
-            if (t.ovl.n) HIP_TRY(hipMemsetAsync(t.ovl.p, 0, t.ovl.bytes(), s));
-            const size_t act = ceil_div(len_active, t.B);
+            const size_t act0 = t.act;
+            if (int r = t.set_active(ceil_div(len_active, t.B), s)) return r;   // update's side effects (:186-190)
             t.last_len = len_active;
-            if (act != t.act) {
-                t.act = act;
+            if (t.act != act0)
                 if (int r = t.rebuild_plan(s)) return r;
-            }
             if (int r = t.patch_device(lists, n, n_cp, other.H.p, src, stride, by_pair, len_data, len_active, s)) return r;
         }
         xf.fade_into(to);
@@ -3550,7 +2943,7 @@ struct SparseMatrixCrossfadeCore {
         if (int r = check_poisoned()) return r;
         uint32_t *lst = lists.idx.data();
         if (int r = a->check_list(n, pair_out, pair_in, lst)) return r;
-        SparseMatrixCore &t = xf.target == 0 ? *b : *a, &base = xf.target == 0 ? *a : *b;
+        Conv &t = other_conv(), &base = target_conv();
         const bool fading = is_crossfading();
         DeviceGuard g(device);
         if (!fading && !response_pending) {
@@ -3577,10 +2970,10 @@ struct SparseMatrixCrossfadeCore {
         if (!fading && stored_len > t.ir_len)
             return fail(FFTCONV_E_INVALID, "New impulse response is longer than initialized length");
         if (int r = order.enter(s)) return r;
-        if (whole && stored_stride == 0 && N > 1) {
+        if (whole && stored_stride == 0 && P > 1) {
             // a shared stored response: every pair gets its own row first
-            for (size_t k = 1; k < N; k *= 2)
-                HIP_TRY(hipMemcpyAsync(stored.p + k * stored_len, stored.p, std::min(k, N - k) * stored_len * sizeof(float),
+            for (size_t k = 1; k < P; k *= 2)
+                HIP_TRY(hipMemcpyAsync(stored.p + k * stored_len, stored.p, std::min(k, P - k) * stored_len * sizeof(float),
                                        hipMemcpyDeviceToDevice, s));
             stored_stride = stored_len;
         }
@@ -3597,16 +2990,16 @@ struct SparseMatrixCrossfadeCore {
         return FFTCONV_OK;
     }
 
-    // Convolution::update (:51-64) from host samples (pair n at src + n * stride,
+    // Convolution::update (:51-64) from host samples (pair p at src + p * stride,
     // stride 0 = one response for every pair); staged in pinned memory and
     // enqueued behind the handle's work: no allocation, no host wait
     int update_host(const float *src, size_t len, size_t stride) {
         if (int r = check_poisoned()) return r;
         DeviceGuard g(device);
-        const bool shared = stride == 0 && N > 1;
-        const size_t rows = shared ? 1 : N;
+        const bool shared = stride == 0 && P > 1;
+        const size_t rows = shared ? 1 : P;
         if (!is_crossfading()) {
-            SparseMatrixCore &t = xf.target == 0 ? *b : *a;
+            Conv &t = other_conv();
             if (len > t.ir_len) return fail(FFTCONV_E_INVALID, "New impulse response is longer than initialized length");
             if (int r = order.enter(stream)) return r;
             if (len)
@@ -3630,7 +3023,7 @@ struct SparseMatrixCrossfadeCore {
 
     // Convolution::update (:51-64) from device samples, stream-ordered (the
     // caller has ordered s behind the handle's previous work)
-    int update_device(const float *src, size_t len, size_t stride, hipStream_t s) {
+    int update_device(const float *src, size_t stride, size_t len, hipStream_t s) {
         if (int r = check_poisoned()) return r;
         if (!is_crossfading()) {
             if (int r = swap_device(src, stride, len, s)) return r;
@@ -3639,11 +3032,11 @@ struct SparseMatrixCrossfadeCore {
             return FFTCONV_OK;
         }
         if (len > stored_len) return fail(FFTCONV_E_INVALID, "assertion failed: response_len <= self.stored_response.len()");
-        const bool shared = stride == 0 && N > 1;
+        const bool shared = stride == 0 && P > 1;
         if (stored.n) HIP_TRY(hipMemsetAsync(stored.p, 0, stored.bytes(), s));
         if (len)
             HIP_TRY(hipMemcpy2DAsync(stored.p, stored_len * sizeof(float), src, (shared ? len : std::max(stride, len)) * sizeof(float),
-                                     len * sizeof(float), shared ? 1 : N, hipMemcpyDeviceToDevice, s));
+                                     len * sizeof(float), shared ? 1 : P, hipMemcpyDeviceToDevice, s));
         stored_stride = shared ? 0 : stored_len;
         response_pending = true;
         book.clear_pending();  // (a whole response replaces a pending partial one)
@@ -3667,10 +3060,10 @@ struct SparseMatrixCrossfadeCore {
         return xf.approaching ? 1 : 2;
     }
     // the path the next process() takes: a pending swap is applied first, and
-    // the path follows from the target convolver's NEW active_seg_count
+    // the path follows from the updated convolver's NEW active_seg_count
     int path_next() const {
         if (!is_crossfading() && response_pending) {
-            const SparseMatrixCore &t = xf.target == 0 ? *b : *a, &other = xf.target == 0 ? *a : *b;
+            const Conv &t = other_conv(), &other = target_conv();
             if (t.ir_len == 0 || stored_len > t.ir_len) return path_now();  // (the update changes nothing)
             const size_t act = ceil_div(stored_len, t.B);
             return fused && in_step && act > 0 && act == other.act && t.cur == other.cur && t.fill == other.fill ? 1 : 0;
@@ -3706,46 +3099,38 @@ struct SparseMatrixCrossfadeCore {
             return FFTCONV_OK;
         }
         if (mx.approaching) mx.vtab = mix_tab.p;  // the call's mix_value walk: launch A of the first chunk fills it
-        MatrixSpXfArgs x{};
-        const SparseMatrixCore *cv[2] = {a.get(), b.get()};
+        typename Conv::XfArgs x{};
+        const Conv *cv[2] = {a.get(), b.get()};
         for (int c = 0; c < 2; ++c) {
             x.H[c] = cv[c]->H.p; x.X[c] = cv[c]->X.p; x.ovl[c] = cv[c]->ovl.p; x.ib[c] = cv[c]->ib.p;
             x.pre[c] = cv[c]->pre.p; x.part[c] = cv[c]->part.p;
         }
-        // (in step: A and B have the same active_seg_count, so their plans are equal)
-        x.rowptr = a->d_rowptr.p; x.col = a->d_col.p; x.plan = a->plan.p; x.wg = a->wg.p;
         x.tw = a->tw.p;
         x.in_stride = (long long)is;
         x.out_stride = (long long)os;
-        x.I = (int)I; x.O = (int)O; x.S = (int)a->S; x.N = (int)N;
-        x.PT = (int)a->PT;
+        x.I = (int)I; x.O = (int)O; x.S = (int)a->S;
         x.act = (int)a->act;
         x.nt_h = Variant::current().nt_matrix(a->H.bytes()) ? 1 : 0;
         x.live = xf.approaching ? 3 : (xf.target == 0 ? 1 : 2);
         x.mix = mx;
-        const size_t B = a->B;
-        size_t processed = 0;
-        while (processed < m) {                                         // FFTConvolver::process :222-294, A and B at once
-            const size_t k = std::min(m - processed, B - a->fill);
-            x.in = din + processed;
-            x.out = dout + processed;
+        a->xf_args(x);
+        for (size_t done = 0; done < m;) {                              // FFTConvolver::process :222-294, A and B at once
+            const size_t k = a->chunk(m - done, a->B);
+            x.in = din + done;
+            x.out = dout + done;
             x.cur = (int)a->cur;
             x.fill = (int)a->fill;
             x.k = (int)k;
-            x.off = (int)processed;
-            x.walk = processed == 0 && mx.approaching ? mix_tab.p : nullptr;
-            if (hipError_t e = launch_matrix_sp_xf_chunk(a->log2b, x, s); e != hipSuccess) {
+            x.off = (int)done;
+            x.walk = done == 0 && mx.approaching ? mix_tab.p : nullptr;
+            if (hipError_t e = Conv::launch_xf_chunk(a->log2b, x, s); e != hipSuccess) {
                 poisoned = true;
                 HIP_TRY(e);
             }
-            a->fill += k;
-            if (a->fill == B) {
-                a->fill = 0;
-                a->cur = a->cur > 0 ? a->cur - 1 : a->act - 1;
-            }
+            a->advance(k, a->B);
             b->fill = a->fill;
             b->cur = a->cur;
-            processed += k;
+            done += k;
         }
         xf.advance(out_len);
         return FFTCONV_OK;
@@ -3770,19 +3155,14 @@ struct SparseMatrixCrossfadeCore {
         return FFTCONV_OK;
     }
 
-    int clone_from(const SparseMatrixCrossfadeCore &o) {
+    int clone_from(const MatrixCrossfadeCoreT &o) {
         DeviceGuard g(o.device);
         if (int r = o.order.drain(o.stream)) return r;
-        device = o.device; I = o.I; O = o.O; N = o.N; max_buffer_size = o.max_buffer_size;
+        device = o.device; I = o.I; O = o.O; P = o.P; max_buffer_size = o.max_buffer_size;
         stored_len = o.stored_len; stored_stride = o.stored_stride; stage_row = o.stage_row;
         xf = o.xf; response_pending = o.response_pending;
         in_step = o.in_step; fused = o.fused; poisoned = o.poisoned;
-        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        a.reset(new (std::nothrow) SparseMatrixCore());
-        b.reset(new (std::nothrow) SparseMatrixCore());
-        if (!a || !b) return fail(FFTCONV_E_NOMEM, "out of host memory");
-        if (int r = a->clone_from(*o.a, stream)) return r;
-        if (int r = b->clone_from(*o.b, stream)) return r;
+        if (int r = clone_convolvers(*o.a, *o.b)) return r;
         if (int r = alloc_buffers(o.hstage.n)) return r;
         book.copy_from(o.book);
         if (stored.n) HIP_TRY(hipMemcpyAsync(stored.p, o.stored.p, stored.bytes(), hipMemcpyDeviceToDevice, stream));
@@ -3790,6 +3170,9 @@ struct SparseMatrixCrossfadeCore {
         return FFTCONV_OK;
     }
 };
+using MatrixCrossfadeCore = MatrixCrossfadeCoreT<MatrixCore>;
+using SparseMatrixCrossfadeCore = MatrixCrossfadeCoreT<SparseMatrixCore>;
+
 
 // ---------------------------------------------------------------------------
 // MatrixTwoStageCore -- I x O TwoStageFFTConvolver instances (o, i) in lockstep
@@ -3976,7 +3359,9 @@ struct MatrixTwoStageCore {
         x.act = (int)h.act;
         x.nt_h = Variant::current().nt_matrix(h.H.bytes()) ? 1 : 0;
         HIP_TRY(launch_matrix_ts_block(h.log2b, x, s));
-        h.cur = h.cur > 0 ? h.cur - 1 : h.act - 1;                              // (:277-291 of both)
+        // a whole block (:277-291 of both); the fused path is taken at h.fill == 0 only (path()),
+        // so this always completes the block and steps `current`
+        h.advance(h.B, h.B);
         t.cur = h.cur;
         precalculated_pos += head_bs;
         tail_input_fill += head_bs;
@@ -4369,6 +3754,122 @@ struct fftconv_matrix_crossfade { MatrixCrossfadeCore core; };
 struct fftconv_matrix_sparse_crossfade { SparseMatrixCrossfadeCore core; };
 struct fftconv_matrix_twostage { MatrixTwoStageCore core; };
 
+// The wrappers the handle types repeat, over the handle struct H (the matrix
+// handles use all of them, the others those whose shape they share).
+namespace {
+
+// where a handle's device, StreamOrder and stream (and a matrix's geometry and
+// state) live: the core itself, or a lookahead core's matrix
+template <class C>
+const C &base(const C &c) { return c; }
+inline const MatrixCore &base(const MatrixLookaheadCore &c) { return c.m; }
+inline const SparseMatrixCore &base(const SparseMatrixLookaheadCore &c) { return c.m; }
+
+template <class H, class... A>
+H *abi_init(A... args) {
+    set_error("");
+    auto *h = new (std::nothrow) H();
+    if (!h) { set_error("out of host memory"); return nullptr; }
+    return make_or_null(h->core.init(args...), h);
+}
+template <class H>
+int abi_update(H *h, const float *responses, size_t len, size_t stride) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.update_host(responses, len, stride);
+}
+// a stream-ordered call: on the handle's device, with the caller's stream
+// ordered behind the handle's previous work, f(core, stream)
+template <class H, class F>
+int abi_on_stream(H *h, void *hip_stream, F f) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    const auto &b = base(h->core);
+    DeviceGuard g(b.device);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (int r = b.order.enter(s)) return r;
+    return f(h->core, s);
+}
+template <class H>
+int abi_update_device(H *h, const float *d_responses, size_t len, size_t stride, void *hip_stream) {
+    return abi_on_stream(h, hip_stream, [&](auto &c, hipStream_t s) { return c.update_device(d_responses, stride, len, s); });
+}
+// both update_pairs variants: d_src == false -- host rows, on the handle's own stream
+template <class H>
+int abi_update_pairs(H *h, size_t n, const uint32_t *pair_out, const uint32_t *pair_in, const float *src, bool d_src,
+                     size_t len, size_t stride, void *hip_stream) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.update_pairs(n, pair_out, pair_in, src, d_src, len, stride,
+                                d_src ? (hipStream_t)hip_stream : base(h->core).stream);
+}
+template <class H>
+int abi_reset(H *h) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    const auto &b = base(h->core);
+    DeviceGuard g(b.device);
+    if (int r = b.order.enter(b.stream)) return r;
+    if (int r = h->core.reset(b.stream)) return r;
+    HIP_TRY(hipStreamSynchronize(b.stream));
+    return FFTCONV_OK;
+}
+template <class H>
+int abi_process(H *h, const float *input, size_t input_len, float *output, size_t output_len) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.process_host(input, input_len, output, output_len);
+}
+template <class H>
+int abi_process_device(H *h, const float *d_in, size_t is, float *d_out, size_t os, size_t len, void *hip_stream) {
+    return abi_on_stream(h, hip_stream, [&](auto &c, hipStream_t s) { return c.process_device(d_in, is, d_out, os, len, s); });
+}
+template <class H>
+int abi_process_device_steps(H *h, const float *d_in, size_t is, size_t in_step, float *d_out, size_t os, size_t out_step,
+                             size_t len, size_t steps, void *hip_stream) {
+    return abi_on_stream(h, hip_stream, [&](auto &c, hipStream_t s) {
+        return matrix_process_device_steps(c, d_in, is, in_step, d_out, os, out_step, len, steps, s);
+    });
+}
+template <class H>
+H *abi_clone(const H *h) {
+    if (!h) { set_error("null handle"); return nullptr; }
+    auto *c = new (std::nothrow) H();
+    if (!c) { set_error("out of host memory"); return nullptr; }
+    return make_or_null(c->core.clone_from(h->core), c);
+}
+template <class H>
+int abi_synchronize(H *h) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    const auto &b = base(h->core);
+    DeviceGuard g(b.device);
+    return b.order.drain(b.stream);
+}
+template <class H>
+int abi_state(const H *h, size_t out3[3]) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    const auto &b = base(h->core);
+    out3[0] = b.cur; out3[1] = b.act; out3[2] = b.fill;
+    return FFTCONV_OK;
+}
+// the crossfaded matrices' CrossfadeConvolver::new and the rest of their own calls
+template <class H, class M>
+H *abi_crossfade_new(const M *convolver, size_t max_response_length, size_t max_buffer_size, size_t crossfade_samples) {
+    if (!convolver) { set_error("null handle"); return nullptr; }
+    auto *h = new (std::nothrow) H();
+    if (!h) { set_error("out of host memory"); return nullptr; }
+    return make_or_null(h->core.init_new(convolver->core, max_response_length, max_buffer_size, crossfade_samples), h);
+}
+template <class H>
+int abi_last_patch(const H *h, size_t out2[2]) {
+    if (!h || !out2) return fail(FFTCONV_E_INVALID, "null handle");
+    out2[0] = h->core.book.last[0];
+    out2[1] = h->core.book.last[1];
+    return FFTCONV_OK;
+}
+template <class H>
+int abi_crossfade_reset(H *h) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return fail(FFTCONV_E_UNIMPLEMENTED, "not yet implemented (CrossfadeConvolver::reset is todo!())");
+}
+
+}  // namespace
+
 extern "C" {
 
 int fftconv_abi_version(void) { return FFTCONV_ABI_VERSION; }
@@ -4489,11 +3990,7 @@ int fftconv_uniform_process(fftconv_uniform *h, const float *input, size_t input
 }
 int fftconv_uniform_process_device(fftconv_uniform *h, const float *d_input, size_t in_stride, float *d_output,
                                    size_t out_stride, size_t len, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.order.enter(s)) return r;
-    return h->core.process_device(d_input, in_stride, d_output, out_stride, len, s);
+    return abi_process_device(h, d_input, in_stride, d_output, out_stride, len, hip_stream);
 }
 int fftconv_uniform_process_device_steps(fftconv_uniform *h, const float *d_input, size_t in_stride, size_t in_step,
                                    float *d_output, size_t out_stride, size_t out_step, size_t len, size_t steps,
@@ -4504,18 +4001,9 @@ int fftconv_uniform_process_device_steps(fftconv_uniform *h, const float *d_inpu
     if (int r = h->core.order.enter(s)) return r;
     return h->core.process_device_steps(d_input, in_stride, in_step, d_output, out_stride, out_step, len, steps, s);
 }
-fftconv_uniform *fftconv_uniform_clone(const fftconv_uniform *h) {
-    if (!h) { set_error("null handle"); return nullptr; }
-    auto *c = new (std::nothrow) fftconv_uniform();
-    if (!c) { set_error("out of host memory"); return nullptr; }
-    return make_or_null(c->core.clone_from(h->core), c);
-}
+fftconv_uniform *fftconv_uniform_clone(const fftconv_uniform *h) { return abi_clone(h); }
 void fftconv_uniform_destroy(fftconv_uniform *h) { delete h; }
-int fftconv_uniform_synchronize(fftconv_uniform *h) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    return h->core.order.drain(h->core.stream);
-}
+int fftconv_uniform_synchronize(fftconv_uniform *h) { return abi_synchronize(h); }
 size_t fftconv_uniform_channels(const fftconv_uniform *h) { return h ? h->core.C : 0; }
 int fftconv_uniform_lookahead_parts(const fftconv_uniform *h) { return h ? h->core.la_W : 0; }
 int fftconv_uniform_far_windows(const fftconv_uniform *h) { return h ? h->core.gw_p : 0; }
@@ -4568,11 +4056,7 @@ int fftconv_twostage_process(fftconv_twostage *h, const float *input, float *out
 }
 int fftconv_twostage_process_device(fftconv_twostage *h, const float *d_input, size_t in_stride, float *d_output,
                                     size_t out_stride, size_t len, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.order.enter(s)) return r;
-    return h->core.process_device(d_input, in_stride, d_output, out_stride, len, s);
+    return abi_process_device(h, d_input, in_stride, d_output, out_stride, len, hip_stream);
 }
 int fftconv_twostage_process_device_steps(fftconv_twostage *h, const float *d_input, size_t in_stride, size_t in_step,
                                    float *d_output, size_t out_stride, size_t out_step, size_t len, size_t steps,
@@ -4583,12 +4067,7 @@ int fftconv_twostage_process_device_steps(fftconv_twostage *h, const float *d_in
     if (int r = h->core.order.enter(s)) return r;
     return h->core.process_device_steps(d_input, in_stride, in_step, d_output, out_stride, out_step, len, steps, s);
 }
-fftconv_twostage *fftconv_twostage_clone(const fftconv_twostage *h) {
-    if (!h) { set_error("null handle"); return nullptr; }
-    auto *c = new (std::nothrow) fftconv_twostage();
-    if (!c) { set_error("out of host memory"); return nullptr; }
-    return make_or_null(c->core.clone_from(h->core), c);
-}
+fftconv_twostage *fftconv_twostage_clone(const fftconv_twostage *h) { return abi_clone(h); }
 void fftconv_twostage_destroy(fftconv_twostage *h) { delete h; }
 int fftconv_twostage_synchronize(fftconv_twostage *h) {
     if (!h) return fail(FFTCONV_E_INVALID, "null handle");
@@ -4698,12 +4177,7 @@ int fftconv_crossfade_process_device_steps(fftconv_crossfade *h, const float *d_
     }
     return FFTCONV_OK;
 }
-fftconv_crossfade *fftconv_crossfade_clone(const fftconv_crossfade *h) {
-    if (!h) { set_error("null handle"); return nullptr; }
-    auto *c = new (std::nothrow) fftconv_crossfade();
-    if (!c) { set_error("out of host memory"); return nullptr; }
-    return make_or_null(c->core.clone_from(h->core), c);
-}
+fftconv_crossfade *fftconv_crossfade_clone(const fftconv_crossfade *h) { return abi_clone(h); }
 void fftconv_crossfade_destroy(fftconv_crossfade *h) { delete h; }
 int fftconv_crossfade_synchronize(fftconv_crossfade *h) {
     if (!h) return fail(FFTCONV_E_INVALID, "null handle");
@@ -4715,173 +4189,93 @@ int fftconv_crossfade_synchronize(fftconv_crossfade *h) {
 fftconv_matrix *fftconv_matrix_init(int device, size_t inputs, size_t outputs, const float *responses,
                                     size_t response_len, size_t response_stride, size_t max_block_size,
                                     size_t max_response_length) {
-    set_error("");
-    auto *h = new (std::nothrow) fftconv_matrix();
-    if (!h) { set_error("out of host memory"); return nullptr; }
-    int r = h->core.init(device, inputs, outputs, responses, response_len, response_stride, max_block_size,
-                         max_response_length);
-    return make_or_null(r, h);
+    return abi_init<fftconv_matrix>(device, inputs, outputs, responses, response_len, response_stride, max_block_size,
+                                    max_response_length);
 }
 int fftconv_matrix_update(fftconv_matrix *h, const float *responses, size_t response_len, size_t response_stride) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.update_host(responses, response_len, response_stride);
+    return abi_update(h, responses, response_len, response_stride);
 }
 int fftconv_matrix_update_device(fftconv_matrix *h, const float *d_responses, size_t response_len,
                                  size_t response_stride, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.order.enter(s)) return r;
-    return h->core.update_device(d_responses, response_stride, response_len, s);
+    return abi_update_device(h, d_responses, response_len, response_stride, hip_stream);
 }
 int fftconv_matrix_update_pairs(fftconv_matrix *h, size_t n_pairs, const uint32_t *pair_out, const uint32_t *pair_in,
                                 const float *responses, size_t response_len, size_t response_stride) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.update_pairs(n_pairs, pair_out, pair_in, responses, false, response_len, response_stride,
-                                h->core.stream);
+    return abi_update_pairs(h, n_pairs, pair_out, pair_in, responses, false, response_len, response_stride, nullptr);
 }
 int fftconv_matrix_update_pairs_device(fftconv_matrix *h, size_t n_pairs, const uint32_t *pair_out,
                                        const uint32_t *pair_in, const float *d_responses, size_t response_len,
                                        size_t response_stride, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.update_pairs(n_pairs, pair_out, pair_in, d_responses, true, response_len, response_stride,
-                                (hipStream_t)hip_stream);
+    return abi_update_pairs(h, n_pairs, pair_out, pair_in, d_responses, true, response_len, response_stride, hip_stream);
 }
-int fftconv_matrix_reset(fftconv_matrix *h) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    if (int r = h->core.order.enter(h->core.stream)) return r;
-    if (int r = h->core.zero_state(h->core.stream)) return r;
-    HIP_TRY(hipStreamSynchronize(h->core.stream));
-    return FFTCONV_OK;
-}
+int fftconv_matrix_reset(fftconv_matrix *h) { return abi_reset(h); }
 int fftconv_matrix_process(fftconv_matrix *h, const float *input, size_t input_len, float *output,
                            size_t output_len) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.process_host(input, input_len, output, output_len);
+    return abi_process(h, input, input_len, output, output_len);
 }
 int fftconv_matrix_process_device(fftconv_matrix *h, const float *d_input, size_t in_stride, float *d_output,
                                   size_t out_stride, size_t len, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.order.enter(s)) return r;
-    return h->core.process_device(d_input, in_stride, d_output, out_stride, len, s);
+    return abi_process_device(h, d_input, in_stride, d_output, out_stride, len, hip_stream);
 }
 int fftconv_matrix_process_device_steps(fftconv_matrix *h, const float *d_input, size_t in_stride, size_t in_step,
                                         float *d_output, size_t out_stride, size_t out_step, size_t len,
                                         size_t steps, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.order.enter(s)) return r;
-    return h->core.process_device_steps(d_input, in_stride, in_step, d_output, out_stride, out_step, len, steps, s);
+    return abi_process_device_steps(h, d_input, in_stride, in_step, d_output, out_stride, out_step, len, steps, hip_stream);
 }
-fftconv_matrix *fftconv_matrix_clone(const fftconv_matrix *h) {
-    if (!h) { set_error("null handle"); return nullptr; }
-    auto *c = new (std::nothrow) fftconv_matrix();
-    if (!c) { set_error("out of host memory"); return nullptr; }
-    return make_or_null(c->core.clone_from(h->core), c);
-}
+fftconv_matrix *fftconv_matrix_clone(const fftconv_matrix *h) { return abi_clone(h); }
 void fftconv_matrix_destroy(fftconv_matrix *h) { delete h; }
-int fftconv_matrix_synchronize(fftconv_matrix *h) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    return h->core.order.drain(h->core.stream);
-}
+int fftconv_matrix_synchronize(fftconv_matrix *h) { return abi_synchronize(h); }
 size_t fftconv_matrix_inputs(const fftconv_matrix *h) { return h ? h->core.I : 0; }
 size_t fftconv_matrix_outputs(const fftconv_matrix *h) { return h ? h->core.O : 0; }
 size_t fftconv_matrix_block_size(const fftconv_matrix *h) { return h ? h->core.B : 0; }
 size_t fftconv_matrix_seg_count(const fftconv_matrix *h) { return h ? h->core.S : 0; }
 int fftconv_matrix_mac_parts(const fftconv_matrix *h) { return h ? h->core.mac_parts() : 0; }
-int fftconv_matrix_state(const fftconv_matrix *h, size_t out3[3]) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    out3[0] = h->core.cur; out3[1] = h->core.act; out3[2] = h->core.fill;
-    return FFTCONV_OK;
-}
+int fftconv_matrix_state(const fftconv_matrix *h, size_t out3[3]) { return abi_state(h, out3); }
 
 // ---- matrix with far-row windows ---------------------------------
 fftconv_matrix_lookahead *fftconv_matrix_lookahead_init(int device, size_t inputs, size_t outputs,
                                                         const float *responses, size_t response_len,
                                                         size_t response_stride, size_t max_block_size,
                                                         size_t max_response_length) {
-    set_error("");
-    auto *h = new (std::nothrow) fftconv_matrix_lookahead();
-    if (!h) { set_error("out of host memory"); return nullptr; }
-    int r = h->core.init(device, inputs, outputs, responses, response_len, response_stride, max_block_size,
-                         max_response_length);
-    return make_or_null(r, h);
+    return abi_init<fftconv_matrix_lookahead>(device, inputs, outputs, responses, response_len, response_stride,
+                                              max_block_size, max_response_length);
 }
 int fftconv_matrix_lookahead_update(fftconv_matrix_lookahead *h, const float *responses, size_t response_len,
                                     size_t response_stride) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.update_host(responses, response_len, response_stride);
+    return abi_update(h, responses, response_len, response_stride);
 }
 int fftconv_matrix_lookahead_update_device(fftconv_matrix_lookahead *h, const float *d_responses, size_t response_len,
                                            size_t response_stride, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.m.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.m.order.enter(s)) return r;
-    return h->core.update_device(d_responses, response_stride, response_len, s);
+    return abi_update_device(h, d_responses, response_len, response_stride, hip_stream);
 }
-int fftconv_matrix_lookahead_reset(fftconv_matrix_lookahead *h) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.m.device);
-    if (int r = h->core.m.order.enter(h->core.m.stream)) return r;
-    if (int r = h->core.reset(h->core.m.stream)) return r;
-    HIP_TRY(hipStreamSynchronize(h->core.m.stream));
-    return FFTCONV_OK;
-}
+int fftconv_matrix_lookahead_reset(fftconv_matrix_lookahead *h) { return abi_reset(h); }
 int fftconv_matrix_lookahead_process(fftconv_matrix_lookahead *h, const float *input, size_t input_len, float *output,
                                      size_t output_len) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.process_host(input, input_len, output, output_len);
+    return abi_process(h, input, input_len, output, output_len);
 }
 int fftconv_matrix_lookahead_process_device(fftconv_matrix_lookahead *h, const float *d_input, size_t in_stride,
                                             float *d_output, size_t out_stride, size_t len, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.m.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.m.order.enter(s)) return r;
-    return h->core.process_device(d_input, in_stride, d_output, out_stride, len, s);
+    return abi_process_device(h, d_input, in_stride, d_output, out_stride, len, hip_stream);
 }
 int fftconv_matrix_lookahead_process_device_steps(fftconv_matrix_lookahead *h, const float *d_input, size_t in_stride,
                                                   size_t in_step, float *d_output, size_t out_stride, size_t out_step,
                                                   size_t len, size_t steps, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.m.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.m.order.enter(s)) return r;
-    return h->core.process_device_steps(d_input, in_stride, in_step, d_output, out_stride, out_step, len, steps, s);
+    return abi_process_device_steps(h, d_input, in_stride, in_step, d_output, out_stride, out_step, len, steps, hip_stream);
 }
-fftconv_matrix_lookahead *fftconv_matrix_lookahead_clone(const fftconv_matrix_lookahead *h) {
-    if (!h) { set_error("null handle"); return nullptr; }
-    auto *c = new (std::nothrow) fftconv_matrix_lookahead();
-    if (!c) { set_error("out of host memory"); return nullptr; }
-    return make_or_null(c->core.clone_from(h->core), c);
-}
+fftconv_matrix_lookahead *fftconv_matrix_lookahead_clone(const fftconv_matrix_lookahead *h) { return abi_clone(h); }
 void fftconv_matrix_lookahead_destroy(fftconv_matrix_lookahead *h) { delete h; }
-int fftconv_matrix_lookahead_synchronize(fftconv_matrix_lookahead *h) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.m.device);
-    return h->core.m.order.drain(h->core.m.stream);
-}
+int fftconv_matrix_lookahead_synchronize(fftconv_matrix_lookahead *h) { return abi_synchronize(h); }
 size_t fftconv_matrix_lookahead_inputs(const fftconv_matrix_lookahead *h) { return h ? h->core.m.I : 0; }
 size_t fftconv_matrix_lookahead_outputs(const fftconv_matrix_lookahead *h) { return h ? h->core.m.O : 0; }
 size_t fftconv_matrix_lookahead_block_size(const fftconv_matrix_lookahead *h) { return h ? h->core.m.B : 0; }
 size_t fftconv_matrix_lookahead_seg_count(const fftconv_matrix_lookahead *h) { return h ? h->core.m.S : 0; }
-int fftconv_matrix_lookahead_state(const fftconv_matrix_lookahead *h, size_t out3[3]) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    out3[0] = h->core.m.cur; out3[1] = h->core.m.act; out3[2] = h->core.m.fill;
-    return FFTCONV_OK;
-}
+int fftconv_matrix_lookahead_state(const fftconv_matrix_lookahead *h, size_t out3[3]) { return abi_state(h, out3); }
 int fftconv_matrix_lookahead_period(void) { return kMatrixLaQ; }
 int fftconv_matrix_lookahead_near_parts(const fftconv_matrix_lookahead *h) { return h ? h->core.near_parts() : 0; }
 int fftconv_matrix_lookahead_far_parts(const fftconv_matrix_lookahead *h) { return h ? h->core.far_parts() : 0; }
 int fftconv_matrix_lookahead_set_windows(fftconv_matrix_lookahead *h, int on) {
     if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    h->core.windows = on != 0;
+    h->core.clk.windows = on != 0;
     return FFTCONV_OK;
 }
 int fftconv_matrix_lookahead_anchors(const fftconv_matrix_lookahead *h) { return h ? h->core.anchors() : 0; }
@@ -4892,95 +4286,53 @@ fftconv_matrix_sparse *fftconv_matrix_sparse_init(int device, size_t inputs, siz
                                                   const float *responses, size_t response_len,
                                                   size_t response_stride, size_t max_block_size,
                                                   size_t max_response_length) {
-    set_error("");
-    auto *h = new (std::nothrow) fftconv_matrix_sparse();
-    if (!h) { set_error("out of host memory"); return nullptr; }
-    int r = h->core.init(device, inputs, outputs, pairs, pair_out, pair_in, responses, response_len, response_stride,
-                         max_block_size, max_response_length);
-    return make_or_null(r, h);
+    return abi_init<fftconv_matrix_sparse>(device, inputs, outputs, pairs, pair_out, pair_in, responses, response_len,
+                                           response_stride, max_block_size, max_response_length);
 }
 int fftconv_matrix_sparse_update(fftconv_matrix_sparse *h, const float *responses, size_t response_len,
                                  size_t response_stride) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.update_host(responses, response_len, response_stride);
+    return abi_update(h, responses, response_len, response_stride);
 }
 int fftconv_matrix_sparse_update_device(fftconv_matrix_sparse *h, const float *d_responses, size_t response_len,
                                         size_t response_stride, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.order.enter(s)) return r;
-    return h->core.update_device(d_responses, response_stride, response_len, s);
+    return abi_update_device(h, d_responses, response_len, response_stride, hip_stream);
 }
 int fftconv_matrix_sparse_update_pairs(fftconv_matrix_sparse *h, size_t n_pairs, const uint32_t *pair_out,
                                        const uint32_t *pair_in, const float *responses, size_t response_len,
                                        size_t response_stride) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.update_pairs(n_pairs, pair_out, pair_in, responses, false, response_len, response_stride,
-                                h->core.stream);
+    return abi_update_pairs(h, n_pairs, pair_out, pair_in, responses, false, response_len, response_stride, nullptr);
 }
 int fftconv_matrix_sparse_update_pairs_device(fftconv_matrix_sparse *h, size_t n_pairs, const uint32_t *pair_out,
                                               const uint32_t *pair_in, const float *d_responses, size_t response_len,
                                               size_t response_stride, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.update_pairs(n_pairs, pair_out, pair_in, d_responses, true, response_len, response_stride,
-                                (hipStream_t)hip_stream);
+    return abi_update_pairs(h, n_pairs, pair_out, pair_in, d_responses, true, response_len, response_stride, hip_stream);
 }
-int fftconv_matrix_sparse_reset(fftconv_matrix_sparse *h) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    if (int r = h->core.order.enter(h->core.stream)) return r;
-    if (int r = h->core.zero_state(h->core.stream)) return r;
-    HIP_TRY(hipStreamSynchronize(h->core.stream));
-    return FFTCONV_OK;
-}
+int fftconv_matrix_sparse_reset(fftconv_matrix_sparse *h) { return abi_reset(h); }
 int fftconv_matrix_sparse_process(fftconv_matrix_sparse *h, const float *input, size_t input_len, float *output,
                                   size_t output_len) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.process_host(input, input_len, output, output_len);
+    return abi_process(h, input, input_len, output, output_len);
 }
 int fftconv_matrix_sparse_process_device(fftconv_matrix_sparse *h, const float *d_input, size_t in_stride,
                                          float *d_output, size_t out_stride, size_t len, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.order.enter(s)) return r;
-    return h->core.process_device(d_input, in_stride, d_output, out_stride, len, s);
+    return abi_process_device(h, d_input, in_stride, d_output, out_stride, len, hip_stream);
 }
 int fftconv_matrix_sparse_process_device_steps(fftconv_matrix_sparse *h, const float *d_input, size_t in_stride,
                                                size_t in_step, float *d_output, size_t out_stride, size_t out_step,
                                                size_t len, size_t steps, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.order.enter(s)) return r;
-    return h->core.process_device_steps(d_input, in_stride, in_step, d_output, out_stride, out_step, len, steps, s);
+    return abi_process_device_steps(h, d_input, in_stride, in_step, d_output, out_stride, out_step, len, steps, hip_stream);
 }
-fftconv_matrix_sparse *fftconv_matrix_sparse_clone(const fftconv_matrix_sparse *h) {
-    if (!h) { set_error("null handle"); return nullptr; }
-    auto *c = new (std::nothrow) fftconv_matrix_sparse();
-    if (!c) { set_error("out of host memory"); return nullptr; }
-    return make_or_null(c->core.clone_from(h->core), c);
-}
+fftconv_matrix_sparse *fftconv_matrix_sparse_clone(const fftconv_matrix_sparse *h) { return abi_clone(h); }
 void fftconv_matrix_sparse_destroy(fftconv_matrix_sparse *h) { delete h; }
-int fftconv_matrix_sparse_synchronize(fftconv_matrix_sparse *h) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    return h->core.order.drain(h->core.stream);
-}
+int fftconv_matrix_sparse_synchronize(fftconv_matrix_sparse *h) { return abi_synchronize(h); }
 size_t fftconv_matrix_sparse_inputs(const fftconv_matrix_sparse *h) { return h ? h->core.I : 0; }
 size_t fftconv_matrix_sparse_outputs(const fftconv_matrix_sparse *h) { return h ? h->core.O : 0; }
-size_t fftconv_matrix_sparse_pairs(const fftconv_matrix_sparse *h) { return h ? h->core.N : 0; }
+size_t fftconv_matrix_sparse_pairs(const fftconv_matrix_sparse *h) { return h ? h->core.P : 0; }
 size_t fftconv_matrix_sparse_block_size(const fftconv_matrix_sparse *h) { return h ? h->core.B : 0; }
 size_t fftconv_matrix_sparse_seg_count(const fftconv_matrix_sparse *h) { return h ? h->core.S : 0; }
 int fftconv_matrix_sparse_output_parts(const fftconv_matrix_sparse *h, size_t output) {
     return h && output < h->core.O ? h->core.output_parts(output) : 0;
 }
-int fftconv_matrix_sparse_state(const fftconv_matrix_sparse *h, size_t out3[3]) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    out3[0] = h->core.cur; out3[1] = h->core.act; out3[2] = h->core.fill;
-    return FFTCONV_OK;
-}
+int fftconv_matrix_sparse_state(const fftconv_matrix_sparse *h, size_t out3[3]) { return abi_state(h, out3); }
 
 // ---- sparse matrix with far-row windows ---------------------------
 fftconv_matrix_sparse_lookahead *fftconv_matrix_sparse_lookahead_init(int device, size_t inputs, size_t outputs,
@@ -4989,88 +4341,52 @@ fftconv_matrix_sparse_lookahead *fftconv_matrix_sparse_lookahead_init(int device
                                                                       size_t response_len, size_t response_stride,
                                                                       size_t max_block_size,
                                                                       size_t max_response_length) {
-    set_error("");
-    auto *h = new (std::nothrow) fftconv_matrix_sparse_lookahead();
-    if (!h) { set_error("out of host memory"); return nullptr; }
-    int r = h->core.init(device, inputs, outputs, pairs, pair_out, pair_in, responses, response_len, response_stride,
-                         max_block_size, max_response_length);
-    return make_or_null(r, h);
+    return abi_init<fftconv_matrix_sparse_lookahead>(device, inputs, outputs, pairs, pair_out, pair_in, responses,
+                                                     response_len, response_stride, max_block_size, max_response_length);
 }
 int fftconv_matrix_sparse_lookahead_update(fftconv_matrix_sparse_lookahead *h, const float *responses,
                                            size_t response_len, size_t response_stride) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.update_host(responses, response_len, response_stride);
+    return abi_update(h, responses, response_len, response_stride);
 }
 int fftconv_matrix_sparse_lookahead_update_device(fftconv_matrix_sparse_lookahead *h, const float *d_responses,
                                                   size_t response_len, size_t response_stride, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.m.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.m.order.enter(s)) return r;
-    return h->core.update_device(d_responses, response_stride, response_len, s);
+    return abi_update_device(h, d_responses, response_len, response_stride, hip_stream);
 }
 int fftconv_matrix_sparse_lookahead_update_pairs(fftconv_matrix_sparse_lookahead *h, size_t n_pairs,
                                                  const uint32_t *pair_out, const uint32_t *pair_in,
                                                  const float *responses, size_t response_len, size_t response_stride) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.update_pairs(n_pairs, pair_out, pair_in, responses, false, response_len, response_stride,
-                                h->core.m.stream);
+    return abi_update_pairs(h, n_pairs, pair_out, pair_in, responses, false, response_len, response_stride, nullptr);
 }
 int fftconv_matrix_sparse_lookahead_update_pairs_device(fftconv_matrix_sparse_lookahead *h, size_t n_pairs,
                                                         const uint32_t *pair_out, const uint32_t *pair_in,
                                                         const float *d_responses, size_t response_len,
                                                         size_t response_stride, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.update_pairs(n_pairs, pair_out, pair_in, d_responses, true, response_len, response_stride,
-                                (hipStream_t)hip_stream);
+    return abi_update_pairs(h, n_pairs, pair_out, pair_in, d_responses, true, response_len, response_stride, hip_stream);
 }
-int fftconv_matrix_sparse_lookahead_reset(fftconv_matrix_sparse_lookahead *h) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.m.device);
-    if (int r = h->core.m.order.enter(h->core.m.stream)) return r;
-    if (int r = h->core.reset(h->core.m.stream)) return r;
-    HIP_TRY(hipStreamSynchronize(h->core.m.stream));
-    return FFTCONV_OK;
-}
+int fftconv_matrix_sparse_lookahead_reset(fftconv_matrix_sparse_lookahead *h) { return abi_reset(h); }
 int fftconv_matrix_sparse_lookahead_process(fftconv_matrix_sparse_lookahead *h, const float *input, size_t input_len,
                                             float *output, size_t output_len) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.process_host(input, input_len, output, output_len);
+    return abi_process(h, input, input_len, output, output_len);
 }
 int fftconv_matrix_sparse_lookahead_process_device(fftconv_matrix_sparse_lookahead *h, const float *d_input,
                                                    size_t in_stride, float *d_output, size_t out_stride, size_t len,
                                                    void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.m.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.m.order.enter(s)) return r;
-    return h->core.process_device(d_input, in_stride, d_output, out_stride, len, s);
+    return abi_process_device(h, d_input, in_stride, d_output, out_stride, len, hip_stream);
 }
 int fftconv_matrix_sparse_lookahead_process_device_steps(fftconv_matrix_sparse_lookahead *h, const float *d_input,
                                                          size_t in_stride, size_t in_step, float *d_output,
                                                          size_t out_stride, size_t out_step, size_t len, size_t steps,
                                                          void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.m.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.m.order.enter(s)) return r;
-    return h->core.process_device_steps(d_input, in_stride, in_step, d_output, out_stride, out_step, len, steps, s);
+    return abi_process_device_steps(h, d_input, in_stride, in_step, d_output, out_stride, out_step, len, steps, hip_stream);
 }
 fftconv_matrix_sparse_lookahead *fftconv_matrix_sparse_lookahead_clone(const fftconv_matrix_sparse_lookahead *h) {
-    if (!h) { set_error("null handle"); return nullptr; }
-    auto *c = new (std::nothrow) fftconv_matrix_sparse_lookahead();
-    if (!c) { set_error("out of host memory"); return nullptr; }
-    return make_or_null(c->core.clone_from(h->core), c);
+    return abi_clone(h);
 }
 void fftconv_matrix_sparse_lookahead_destroy(fftconv_matrix_sparse_lookahead *h) { delete h; }
-int fftconv_matrix_sparse_lookahead_synchronize(fftconv_matrix_sparse_lookahead *h) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.m.device);
-    return h->core.m.order.drain(h->core.m.stream);
-}
+int fftconv_matrix_sparse_lookahead_synchronize(fftconv_matrix_sparse_lookahead *h) { return abi_synchronize(h); }
 size_t fftconv_matrix_sparse_lookahead_inputs(const fftconv_matrix_sparse_lookahead *h) { return h ? h->core.m.I : 0; }
 size_t fftconv_matrix_sparse_lookahead_outputs(const fftconv_matrix_sparse_lookahead *h) { return h ? h->core.m.O : 0; }
-size_t fftconv_matrix_sparse_lookahead_pairs(const fftconv_matrix_sparse_lookahead *h) { return h ? h->core.m.N : 0; }
+size_t fftconv_matrix_sparse_lookahead_pairs(const fftconv_matrix_sparse_lookahead *h) { return h ? h->core.m.P : 0; }
 size_t fftconv_matrix_sparse_lookahead_block_size(const fftconv_matrix_sparse_lookahead *h) {
     return h ? h->core.m.B : 0;
 }
@@ -5078,9 +4394,7 @@ size_t fftconv_matrix_sparse_lookahead_seg_count(const fftconv_matrix_sparse_loo
     return h ? h->core.m.S : 0;
 }
 int fftconv_matrix_sparse_lookahead_state(const fftconv_matrix_sparse_lookahead *h, size_t out3[3]) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    out3[0] = h->core.m.cur; out3[1] = h->core.m.act; out3[2] = h->core.m.fill;
-    return FFTCONV_OK;
+    return abi_state(h, out3);
 }
 int fftconv_matrix_sparse_lookahead_near_parts(const fftconv_matrix_sparse_lookahead *h, size_t output) {
     return h && output < h->core.m.O ? h->core.near_parts(output) : 0;
@@ -5090,7 +4404,7 @@ int fftconv_matrix_sparse_lookahead_far_parts(const fftconv_matrix_sparse_lookah
 }
 int fftconv_matrix_sparse_lookahead_set_windows(fftconv_matrix_sparse_lookahead *h, int on) {
     if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    h->core.windows = on != 0;
+    h->core.clk.windows = on != 0;
     return FFTCONV_OK;
 }
 int fftconv_matrix_sparse_lookahead_anchors(const fftconv_matrix_sparse_lookahead *h) {
@@ -5112,90 +4426,51 @@ fftconv_matrix_crossfade *fftconv_matrix_crossfade_init(int device, size_t input
 }
 fftconv_matrix_crossfade *fftconv_matrix_crossfade_new(const fftconv_matrix *convolver, size_t max_response_length,
                                                        size_t max_buffer_size, size_t crossfade_samples) {
-    if (!convolver) { set_error("null handle"); return nullptr; }
-    auto *h = new (std::nothrow) fftconv_matrix_crossfade();
-    if (!h) { set_error("out of host memory"); return nullptr; }
-    return make_or_null(h->core.init_new(convolver->core, max_response_length, max_buffer_size, crossfade_samples), h);
+    return abi_crossfade_new<fftconv_matrix_crossfade>(convolver, max_response_length, max_buffer_size, crossfade_samples);
 }
 int fftconv_matrix_crossfade_update(fftconv_matrix_crossfade *h, const float *responses, size_t response_len,
                                     size_t response_stride) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.update_host(responses, response_len, response_stride);
+    return abi_update(h, responses, response_len, response_stride);
 }
 int fftconv_matrix_crossfade_update_device(fftconv_matrix_crossfade *h, const float *d_responses, size_t response_len,
                                            size_t response_stride, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.order.enter(s)) return r;
-    return h->core.update_device(d_responses, response_len, response_stride, s);
+    return abi_update_device(h, d_responses, response_len, response_stride, hip_stream);
 }
 int fftconv_matrix_crossfade_update_pairs(fftconv_matrix_crossfade *h, size_t n_pairs, const uint32_t *pair_out,
                                           const uint32_t *pair_in, const float *responses, size_t response_len,
                                           size_t response_stride) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.update_pairs(n_pairs, pair_out, pair_in, responses, false, response_len, response_stride,
-                                h->core.stream);
+    return abi_update_pairs(h, n_pairs, pair_out, pair_in, responses, false, response_len, response_stride, nullptr);
 }
 int fftconv_matrix_crossfade_update_pairs_device(fftconv_matrix_crossfade *h, size_t n_pairs, const uint32_t *pair_out,
                                                  const uint32_t *pair_in, const float *d_responses,
                                                  size_t response_len, size_t response_stride, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.update_pairs(n_pairs, pair_out, pair_in, d_responses, true, response_len, response_stride,
-                                (hipStream_t)hip_stream);
+    return abi_update_pairs(h, n_pairs, pair_out, pair_in, d_responses, true, response_len, response_stride, hip_stream);
 }
 size_t fftconv_matrix_crossfade_diff_pairs(const fftconv_matrix_crossfade *h) { return h ? h->core.book.nd : 0; }
 int fftconv_matrix_crossfade_last_patch(const fftconv_matrix_crossfade *h, size_t out2[2]) {
-    if (!h || !out2) return fail(FFTCONV_E_INVALID, "null handle");
-    out2[0] = h->core.book.last[0];
-    out2[1] = h->core.book.last[1];
-    return FFTCONV_OK;
+    return abi_last_patch(h, out2);
 }
-int fftconv_matrix_crossfade_reset(fftconv_matrix_crossfade *h) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return fail(FFTCONV_E_UNIMPLEMENTED, "not yet implemented (CrossfadeConvolver::reset is todo!())");
-}
+int fftconv_matrix_crossfade_reset(fftconv_matrix_crossfade *h) { return abi_crossfade_reset(h); }
 int fftconv_matrix_crossfade_process(fftconv_matrix_crossfade *h, const float *input, size_t input_len, float *output,
                                      size_t output_len) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.process_host(input, input_len, output, output_len);
+    return abi_process(h, input, input_len, output, output_len);
 }
 int fftconv_matrix_crossfade_process_device(fftconv_matrix_crossfade *h, const float *d_input, size_t in_stride,
                                             float *d_output, size_t out_stride, size_t output_len, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.order.enter(s)) return r;
-    return h->core.process_device(d_input, in_stride, d_output, out_stride, output_len, s);
+    return abi_process_device(h, d_input, in_stride, d_output, out_stride, output_len, hip_stream);
 }
 int fftconv_matrix_crossfade_process_device_steps(fftconv_matrix_crossfade *h, const float *d_input, size_t in_stride,
                                                   size_t in_step, float *d_output, size_t out_stride, size_t out_step,
                                                   size_t output_len, size_t steps, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.order.enter(s)) return r;
-    for (size_t k = 0; k < steps; ++k)
-        if (int r = h->core.process_device(d_input + k * in_step, in_stride, d_output + k * out_step, out_stride,
-                                           output_len, s))
-            return r;
-    return FFTCONV_OK;
+    return abi_process_device_steps(h, d_input, in_stride, in_step, d_output, out_stride, out_step, output_len, steps,
+                                    hip_stream);
 }
 int fftconv_matrix_crossfade_is_crossfading(const fftconv_matrix_crossfade *h) {
     return h && h->core.is_crossfading() ? 1 : 0;
 }
-fftconv_matrix_crossfade *fftconv_matrix_crossfade_clone(const fftconv_matrix_crossfade *h) {
-    if (!h) { set_error("null handle"); return nullptr; }
-    auto *c = new (std::nothrow) fftconv_matrix_crossfade();
-    if (!c) { set_error("out of host memory"); return nullptr; }
-    return make_or_null(c->core.clone_from(h->core), c);
-}
+fftconv_matrix_crossfade *fftconv_matrix_crossfade_clone(const fftconv_matrix_crossfade *h) { return abi_clone(h); }
 void fftconv_matrix_crossfade_destroy(fftconv_matrix_crossfade *h) { delete h; }
-int fftconv_matrix_crossfade_synchronize(fftconv_matrix_crossfade *h) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    return h->core.quiesce();
-}
+int fftconv_matrix_crossfade_synchronize(fftconv_matrix_crossfade *h) { return abi_synchronize(h); }
 size_t fftconv_matrix_crossfade_inputs(const fftconv_matrix_crossfade *h) { return h ? h->core.I : 0; }
 size_t fftconv_matrix_crossfade_outputs(const fftconv_matrix_crossfade *h) { return h ? h->core.O : 0; }
 int fftconv_matrix_crossfade_set_fused(fftconv_matrix_crossfade *h, int on) {
@@ -5226,99 +4501,63 @@ fftconv_matrix_sparse_crossfade *fftconv_matrix_sparse_crossfade_new(const fftco
                                                                      size_t max_response_length,
                                                                      size_t max_buffer_size,
                                                                      size_t crossfade_samples) {
-    if (!convolver) { set_error("null handle"); return nullptr; }
-    auto *h = new (std::nothrow) fftconv_matrix_sparse_crossfade();
-    if (!h) { set_error("out of host memory"); return nullptr; }
-    return make_or_null(h->core.init_new(convolver->core, max_response_length, max_buffer_size, crossfade_samples), h);
+    return abi_crossfade_new<fftconv_matrix_sparse_crossfade>(convolver, max_response_length, max_buffer_size,
+                                                              crossfade_samples);
 }
 int fftconv_matrix_sparse_crossfade_update(fftconv_matrix_sparse_crossfade *h, const float *responses,
                                            size_t response_len, size_t response_stride) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.update_host(responses, response_len, response_stride);
+    return abi_update(h, responses, response_len, response_stride);
 }
 int fftconv_matrix_sparse_crossfade_update_device(fftconv_matrix_sparse_crossfade *h, const float *d_responses,
                                                   size_t response_len, size_t response_stride, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.order.enter(s)) return r;
-    return h->core.update_device(d_responses, response_len, response_stride, s);
+    return abi_update_device(h, d_responses, response_len, response_stride, hip_stream);
 }
 int fftconv_matrix_sparse_crossfade_update_pairs(fftconv_matrix_sparse_crossfade *h, size_t n_pairs,
                                                  const uint32_t *pair_out, const uint32_t *pair_in,
                                                  const float *responses, size_t response_len,
                                                  size_t response_stride) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.update_pairs(n_pairs, pair_out, pair_in, responses, false, response_len, response_stride,
-                                h->core.stream);
+    return abi_update_pairs(h, n_pairs, pair_out, pair_in, responses, false, response_len, response_stride, nullptr);
 }
 int fftconv_matrix_sparse_crossfade_update_pairs_device(fftconv_matrix_sparse_crossfade *h, size_t n_pairs,
                                                         const uint32_t *pair_out, const uint32_t *pair_in,
                                                         const float *d_responses, size_t response_len,
                                                         size_t response_stride, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.update_pairs(n_pairs, pair_out, pair_in, d_responses, true, response_len, response_stride,
-                                (hipStream_t)hip_stream);
+    return abi_update_pairs(h, n_pairs, pair_out, pair_in, d_responses, true, response_len, response_stride, hip_stream);
 }
 size_t fftconv_matrix_sparse_crossfade_diff_pairs(const fftconv_matrix_sparse_crossfade *h) {
     return h ? h->core.book.nd : 0;
 }
 int fftconv_matrix_sparse_crossfade_last_patch(const fftconv_matrix_sparse_crossfade *h, size_t out2[2]) {
-    if (!h || !out2) return fail(FFTCONV_E_INVALID, "null handle");
-    out2[0] = h->core.book.last[0];
-    out2[1] = h->core.book.last[1];
-    return FFTCONV_OK;
+    return abi_last_patch(h, out2);
 }
-int fftconv_matrix_sparse_crossfade_reset(fftconv_matrix_sparse_crossfade *h) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return fail(FFTCONV_E_UNIMPLEMENTED, "not yet implemented (CrossfadeConvolver::reset is todo!())");
-}
+int fftconv_matrix_sparse_crossfade_reset(fftconv_matrix_sparse_crossfade *h) { return abi_crossfade_reset(h); }
 int fftconv_matrix_sparse_crossfade_process(fftconv_matrix_sparse_crossfade *h, const float *input, size_t input_len,
                                             float *output, size_t output_len) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    return h->core.process_host(input, input_len, output, output_len);
+    return abi_process(h, input, input_len, output, output_len);
 }
 int fftconv_matrix_sparse_crossfade_process_device(fftconv_matrix_sparse_crossfade *h, const float *d_input,
                                                    size_t in_stride, float *d_output, size_t out_stride,
                                                    size_t output_len, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.order.enter(s)) return r;
-    return h->core.process_device(d_input, in_stride, d_output, out_stride, output_len, s);
+    return abi_process_device(h, d_input, in_stride, d_output, out_stride, output_len, hip_stream);
 }
 int fftconv_matrix_sparse_crossfade_process_device_steps(fftconv_matrix_sparse_crossfade *h, const float *d_input,
                                                          size_t in_stride, size_t in_step, float *d_output,
                                                          size_t out_stride, size_t out_step, size_t output_len,
                                                          size_t steps, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.order.enter(s)) return r;
-    for (size_t k = 0; k < steps; ++k)
-        if (int r = h->core.process_device(d_input + k * in_step, in_stride, d_output + k * out_step, out_stride,
-                                           output_len, s))
-            return r;
-    return FFTCONV_OK;
+    return abi_process_device_steps(h, d_input, in_stride, in_step, d_output, out_stride, out_step, output_len, steps,
+                                    hip_stream);
 }
 int fftconv_matrix_sparse_crossfade_is_crossfading(const fftconv_matrix_sparse_crossfade *h) {
     return h && h->core.is_crossfading() ? 1 : 0;
 }
 fftconv_matrix_sparse_crossfade *fftconv_matrix_sparse_crossfade_clone(const fftconv_matrix_sparse_crossfade *h) {
-    if (!h) { set_error("null handle"); return nullptr; }
-    auto *c = new (std::nothrow) fftconv_matrix_sparse_crossfade();
-    if (!c) { set_error("out of host memory"); return nullptr; }
-    return make_or_null(c->core.clone_from(h->core), c);
+    return abi_clone(h);
 }
 void fftconv_matrix_sparse_crossfade_destroy(fftconv_matrix_sparse_crossfade *h) { delete h; }
-int fftconv_matrix_sparse_crossfade_synchronize(fftconv_matrix_sparse_crossfade *h) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    return h->core.quiesce();
-}
+int fftconv_matrix_sparse_crossfade_synchronize(fftconv_matrix_sparse_crossfade *h) { return abi_synchronize(h); }
 size_t fftconv_matrix_sparse_crossfade_inputs(const fftconv_matrix_sparse_crossfade *h) { return h ? h->core.I : 0; }
 size_t fftconv_matrix_sparse_crossfade_outputs(const fftconv_matrix_sparse_crossfade *h) { return h ? h->core.O : 0; }
-size_t fftconv_matrix_sparse_crossfade_pairs(const fftconv_matrix_sparse_crossfade *h) { return h ? h->core.N : 0; }
+size_t fftconv_matrix_sparse_crossfade_pairs(const fftconv_matrix_sparse_crossfade *h) { return h ? h->core.P : 0; }
 int fftconv_matrix_sparse_crossfade_set_fused(fftconv_matrix_sparse_crossfade *h, int on) {
     if (!h) return fail(FFTCONV_E_INVALID, "null handle");
     h->core.fused = on != 0;
@@ -5327,6 +4566,7 @@ int fftconv_matrix_sparse_crossfade_set_fused(fftconv_matrix_sparse_crossfade *h
 int fftconv_matrix_sparse_crossfade_path(const fftconv_matrix_sparse_crossfade *h) {
     return h ? h->core.path_next() : 0;
 }
+
 
 // ---- matrix two-stage ---------------------------------------------
 fftconv_matrix_twostage *fftconv_matrix_twostage_init(int device, size_t inputs, size_t outputs,
@@ -5354,11 +4594,7 @@ int fftconv_matrix_twostage_process(fftconv_matrix_twostage *h, const float *inp
 }
 int fftconv_matrix_twostage_process_device(fftconv_matrix_twostage *h, const float *d_input, size_t in_stride,
                                            float *d_output, size_t out_stride, size_t len, void *hip_stream) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (int r = h->core.order.enter(s)) return r;
-    return h->core.process_device(d_input, in_stride, d_output, out_stride, len, s);
+    return abi_process_device(h, d_input, in_stride, d_output, out_stride, len, hip_stream);
 }
 int fftconv_matrix_twostage_process_device_steps(fftconv_matrix_twostage *h, const float *d_input, size_t in_stride,
                                                  size_t in_step, float *d_output, size_t out_stride, size_t out_step,
@@ -5369,18 +4605,9 @@ int fftconv_matrix_twostage_process_device_steps(fftconv_matrix_twostage *h, con
     if (int r = h->core.order.enter(s)) return r;
     return h->core.process_device_steps(d_input, in_stride, in_step, d_output, out_stride, out_step, len, steps, s);
 }
-fftconv_matrix_twostage *fftconv_matrix_twostage_clone(const fftconv_matrix_twostage *h) {
-    if (!h) { set_error("null handle"); return nullptr; }
-    auto *c = new (std::nothrow) fftconv_matrix_twostage();
-    if (!c) { set_error("out of host memory"); return nullptr; }
-    return make_or_null(c->core.clone_from(h->core), c);
-}
+fftconv_matrix_twostage *fftconv_matrix_twostage_clone(const fftconv_matrix_twostage *h) { return abi_clone(h); }
 void fftconv_matrix_twostage_destroy(fftconv_matrix_twostage *h) { delete h; }
-int fftconv_matrix_twostage_synchronize(fftconv_matrix_twostage *h) {
-    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
-    DeviceGuard g(h->core.device);
-    return h->core.order.drain(h->core.stream);
-}
+int fftconv_matrix_twostage_synchronize(fftconv_matrix_twostage *h) { return abi_synchronize(h); }
 size_t fftconv_matrix_twostage_inputs(const fftconv_matrix_twostage *h) { return h ? h->core.I : 0; }
 size_t fftconv_matrix_twostage_outputs(const fftconv_matrix_twostage *h) { return h ? h->core.O : 0; }
 size_t fftconv_matrix_twostage_tail_block_size(const fftconv_matrix_twostage *h) { return h ? h->core.T : 0; }

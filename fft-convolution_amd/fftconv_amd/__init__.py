@@ -664,143 +664,210 @@ class _UpdatePairs:
                                                C.c_void_p(stream) if stream else None))
 
 
-class MatrixConvolver(_UpdatePairs, _Base):
+def _dense_responses(responses, inputs=None, outputs=None):
+    r = _f32(responses)
+    if r.ndim != 3 or (inputs is not None and r.shape[:2] != (outputs, inputs)):
+        raise ValueError("responses must be [outputs][inputs][len]")
+    return r
+
+
+def _listed_responses(responses, pairs: int):
+    r = _f32(responses)
+    if r.ndim != 2 or r.shape[0] != pairs:
+        raise ValueError("responses must be [pairs][len]")
+    return r
+
+
+class _MatrixBase(_Base):
+    """What the matrix classes share: inputs x outputs, a whole update, reset,
+    process and clone, each through the class's C prefix.  A
+    dense matrix takes its responses as [O][I][len] (pair o * inputs + i); a
+    class with a listed pair set (`pairs` is its size) as [pairs][len], in list
+    order."""
+
+    pairs = None
+
+    def __init__(self, h, inputs: int, outputs: int):
+        super().__init__(h, inputs)
+        self.inputs = inputs
+        self.outputs = outputs
+
+    @classmethod
+    def _cfn(cls, name):
+        return getattr(lib(), f"fftconv_{cls._prefix}_{name}")
+
+    def _set_pair_list(self, pair_list, pairs: int | None = None):
+        self._pair_list = [(int(o), int(i)) for o, i in pair_list] if pair_list is not None else None
+        self.pairs = len(self._pair_list) if pairs is None else pairs
+
+    def _clone_args(self):
+        """The constructor's arguments after the handle."""
+        return self.inputs, self.outputs
+
+    def update(self, responses):
+        """update() of every pair with responses[O][I][len], or [pairs][len]
+        over a listed pair set (whole matrix).  A crossfaded matrix (:51-64)
+        starts the fade, or stores the responses until the fade under way has
+        ended."""
+        if self.pairs is None:
+            r = _dense_responses(responses, self.inputs, self.outputs)
+        else:
+            r = _listed_responses(responses, self.pairs)
+        _check(self._fn("update")(self._h, _p(r), r.shape[-1], r.shape[-1]))
+
+    def update_device(self, d_responses: int, response_len: int, stride: int = 0, stream: int = 0):
+        """update() from device memory (pair p -- o * inputs + i, or the
+        position in the pair list -- at d_responses + 4 * p * stride; stride 0 =
+        one response for every pair), stream-ordered."""
+        _check(self._fn("update_device")(self._h, C.c_void_p(d_responses), response_len, stride,
+                                         C.c_void_p(stream) if stream else None))
+
+    def reset(self):
+        _check(self._fn("reset")(self._h))
+
+    def process(self, inp, out_len: int | None = None) -> np.ndarray:
+        """x[inputs][n] -> y[outputs][out_len or n].  (A crossfaded matrix: n >=
+        max_buffer_size, and the state advances by max_buffer_size samples
+        whatever out_len is.)"""
+        x = _f32(inp)
+        if x.ndim != 2 or x.shape[0] != self.inputs:
+            raise ValueError(f"input must be [{self.inputs}][n]")
+        n_in = x.shape[1]
+        n = n_in if out_len is None else out_len
+        y = np.zeros((self.outputs, n), np.float32)
+        _check(self._fn("process")(self._h, _p(x), n_in, _p(y), n))
+        return y
+
+    def clone(self):
+        return type(self)(_handle(self._fn("clone")(self._h)), *self._clone_args())
+
+
+class _MatrixGeometry(_MatrixBase):
+    """block_size, seg_count and state() of the matrices that are one convolver
+    (the C ABI has none for a crossfaded matrix)."""
+
+    @property
+    def block_size(self) -> int:
+        return int(self._fn("block_size")(self._h))
+
+    @property
+    def seg_count(self) -> int:
+        return int(self._fn("seg_count")(self._h))
+
+    def state(self):
+        """(current, active_seg_count, input_buffer_fill) of the whole matrix."""
+        out = (C.c_size_t * 3)()
+        _check(self._fn("state")(self._h, out))
+        return tuple(int(v) for v in out)
+
+
+class _MatrixWindows:
+    """The far-row windows' controls of the two lookahead matrices."""
+
+    @staticmethod
+    def period() -> int:
+        """Q: rows s >= Q are far rows, an output anchors once every Q blocks."""
+        return int(lib().fftconv_matrix_lookahead_period())
+
+    def set_windows(self, on: bool):
+        """off: every output sums its far rows in full on every block (the same bits)."""
+        _check(self._fn("set_windows")(self._h, 1 if on else 0))
+
+    def anchors(self) -> int:
+        """Outputs (with at least one pair) that anchor when the next block starts."""
+        return int(self._fn("anchors")(self._h))
+
+
+class _MatrixCrossfade(_UpdatePairs):
+    """What the two crossfaded matrices share.  `_all_pairs()` lists the
+    handle's (output, input) pairs in pair order."""
+
+    def update_input(self, i: int, responses):
+        """update_pairs of every pair that reads input i, in pair order: responses[those pairs][len]."""
+        self.update_pairs([p for p in self._all_pairs() if p[1] == i], responses)
+
+    def update_output(self, o: int, responses):
+        """update_pairs of every pair that feeds output o, in pair order: responses[those pairs][len]."""
+        self.update_pairs([p for p in self._all_pairs() if p[0] == o], responses)
+
+    def diff_pairs(self) -> int:
+        """|D|: the pairs whose spectra may differ between the two convolvers."""
+        return int(self._fn("diff_pairs")(self._h))
+
+    def last_patch(self):
+        """(pairs transformed, pairs copied) by the last applied swap."""
+        out = (C.c_size_t * 2)()
+        _check(self._fn("last_patch")(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def is_crossfading(self) -> bool:
+        return bool(self._fn("is_crossfading")(self._h))
+
+    def set_fused(self, on: bool):
+        """False: every call takes the composition path (tests, A/B runs)."""
+        _check(self._fn("set_fused")(self._h, 1 if on else 0))
+
+    def path(self) -> int:
+        """The path the next process() takes: 0 composition, 1 fused with both
+        convolvers live, 2 fused with one convolver idle."""
+        return int(self._fn("path")(self._h))
+
+
+class _DenseMatrix(_MatrixGeometry):
+    """init of the plain and the lookahead dense matrix."""
+
+    @classmethod
+    def init(cls, responses, max_block_size: int, max_response_length: int, device: int = 0):
+        """responses[O][I][len]: h[o][i] is the response from input i to output o."""
+        r = _dense_responses(responses)
+        O, I, n = r.shape
+        h = cls._cfn("init")(device, I, O, _p(r), n, n, max_block_size, max_response_length)
+        return cls(_handle(h), I, O)
+
+
+class _ListedMatrix(_UpdatePairs, _MatrixGeometry):
+    """Construction of the plain and the lookahead matrix over a listed pair set."""
+
+    def __init__(self, h, inputs: int, outputs: int, pairs: int, pair_list=None):
+        super().__init__(h, inputs, outputs)
+        self._set_pair_list(pair_list, pairs)
+
+    def _clone_args(self):
+        return self.inputs, self.outputs, self.pairs, self._pair_list
+
+    @classmethod
+    def init(cls, pairs, responses, inputs: int, outputs: int, max_block_size: int, max_response_length: int,
+             device: int = 0):
+        """pairs: (output, input) tuples, strictly ascending; responses[n] is
+        the response of pairs[n]."""
+        po, pi = _pair_arrays(pairs)
+        r = _listed_responses(responses, len(po))
+        n = r.shape[1]
+        h = cls._cfn("init")(device, inputs, outputs, len(po), po.ctypes.data_as(_u32p), pi.ctypes.data_as(_u32p),
+                             _p(r), n, n, max_block_size, max_response_length)
+        return cls(_handle(h), inputs, outputs, len(po), list(zip(po.tolist(), pi.tolist())))
+
+
+class MatrixConvolver(_UpdatePairs, _DenseMatrix):
     """Multi-input multi-output partitioned convolution (fftconv.h,
     "MatrixConvolver"): y[o] = sum_i x[i] * h[o][i], as inputs x outputs
     FFTConvolver instances in lockstep with one delay line per input."""
 
     _prefix = "matrix"
 
-    def __init__(self, h, inputs: int, outputs: int):
-        super().__init__(h, inputs)
-        self.inputs = inputs
-        self.outputs = outputs
-
-    @staticmethod
-    def _pairs(responses, inputs=None, outputs=None):
-        r = _f32(responses)
-        if r.ndim != 3 or (inputs is not None and r.shape[:2] != (outputs, inputs)):
-            raise ValueError("responses must be [outputs][inputs][len]")
-        return r
-
-    @classmethod
-    def init(cls, responses, max_block_size: int, max_response_length: int, device: int = 0):
-        """responses[O][I][len]: h[o][i] is the response from input i to output o."""
-        r = cls._pairs(responses)
-        O, I, n = r.shape
-        h = lib().fftconv_matrix_init(device, I, O, _p(r), n, n, max_block_size, max_response_length)
-        return cls(_handle(h), I, O)
-
-    def update(self, responses):
-        """update() of every pair with responses[O][I][len]."""
-        r = self._pairs(responses, self.inputs, self.outputs)
-        _check(lib().fftconv_matrix_update(self._h, _p(r), r.shape[2], r.shape[2]))
-
-    def update_device(self, d_responses: int, response_len: int, stride: int = 0, stream: int = 0):
-        """update() from device memory (pair o * inputs + i at d_responses +
-        4 * pair * stride; stride 0 = one response for every pair), stream-ordered."""
-        _check(self._fn("update_device")(self._h, C.c_void_p(d_responses), response_len, stride,
-                                         C.c_void_p(stream) if stream else None))
-
-    def reset(self):
-        _check(lib().fftconv_matrix_reset(self._h))
-
-    def process(self, inp, out_len: int | None = None) -> np.ndarray:
-        """x[inputs][n] -> y[outputs][out_len or n]."""
-        x = _f32(inp)
-        if x.ndim != 2 or x.shape[0] != self.inputs:
-            raise ValueError(f"input must be [{self.inputs}][n]")
-        n_in = x.shape[1]
-        n = n_in if out_len is None else out_len
-        y = np.zeros((self.outputs, n), np.float32)
-        _check(lib().fftconv_matrix_process(self._h, _p(x), n_in, _p(y), n))
-        return y
-
-    def clone(self):
-        return MatrixConvolver(_handle(lib().fftconv_matrix_clone(self._h)), self.inputs, self.outputs)
-
-    @property
-    def block_size(self) -> int:
-        return int(lib().fftconv_matrix_block_size(self._h))
-
-    @property
-    def seg_count(self) -> int:
-        return int(lib().fftconv_matrix_seg_count(self._h))
-
     @property
     def mac_parts(self) -> int:
         """Workgroups sharing one output's spectral sum, for the current active_seg_count."""
         return int(lib().fftconv_matrix_mac_parts(self._h))
 
-    def state(self):
-        """(current, active_seg_count, input_buffer_fill) of the whole matrix."""
-        out = (C.c_size_t * 3)()
-        _check(lib().fftconv_matrix_state(self._h, out))
-        return tuple(int(v) for v in out)
 
-
-class MatrixLookaheadConvolver(_Base):
+class MatrixLookaheadConvolver(_MatrixWindows, _DenseMatrix):
     """The MatrixConvolver with far-row windows (fftconv.h,
     "MatrixLookaheadConvolver"): the same inputs x outputs FFTConvolver instances
     in lockstep, but an output's rows s >= period are summed once every `period`
     blocks for the next `period` blocks.  Blocks 32..512."""
 
     _prefix = "matrix_lookahead"
-
-    def __init__(self, h, inputs: int, outputs: int):
-        super().__init__(h, inputs)
-        self.inputs = inputs
-        self.outputs = outputs
-
-    @classmethod
-    def init(cls, responses, max_block_size: int, max_response_length: int, device: int = 0):
-        """responses[O][I][len]: h[o][i] is the response from input i to output o."""
-        r = MatrixConvolver._pairs(responses)
-        O, I, n = r.shape
-        h = lib().fftconv_matrix_lookahead_init(device, I, O, _p(r), n, n, max_block_size, max_response_length)
-        return cls(_handle(h), I, O)
-
-    def update(self, responses):
-        """update() of every pair with responses[O][I][len] (whole matrix only)."""
-        r = MatrixConvolver._pairs(responses, self.inputs, self.outputs)
-        _check(lib().fftconv_matrix_lookahead_update(self._h, _p(r), r.shape[2], r.shape[2]))
-
-    def update_device(self, d_responses: int, response_len: int, stride: int = 0, stream: int = 0):
-        """update() from device memory (pair o * inputs + i at d_responses +
-        4 * pair * stride; stride 0 = one response for every pair), stream-ordered."""
-        _check(self._fn("update_device")(self._h, C.c_void_p(d_responses), response_len, stride,
-                                         C.c_void_p(stream) if stream else None))
-
-    def reset(self):
-        _check(lib().fftconv_matrix_lookahead_reset(self._h))
-
-    def process(self, inp, out_len: int | None = None) -> np.ndarray:
-        """x[inputs][n] -> y[outputs][out_len or n]."""
-        x = _f32(inp)
-        if x.ndim != 2 or x.shape[0] != self.inputs:
-            raise ValueError(f"input must be [{self.inputs}][n]")
-        n_in = x.shape[1]
-        n = n_in if out_len is None else out_len
-        y = np.zeros((self.outputs, n), np.float32)
-        _check(lib().fftconv_matrix_lookahead_process(self._h, _p(x), n_in, _p(y), n))
-        return y
-
-    def clone(self):
-        return MatrixLookaheadConvolver(_handle(lib().fftconv_matrix_lookahead_clone(self._h)), self.inputs,
-                                        self.outputs)
-
-    @property
-    def block_size(self) -> int:
-        return int(lib().fftconv_matrix_lookahead_block_size(self._h))
-
-    @property
-    def seg_count(self) -> int:
-        return int(lib().fftconv_matrix_lookahead_seg_count(self._h))
-
-    @staticmethod
-    def period() -> int:
-        """Q: rows s >= Q are far rows, an output anchors once every Q blocks."""
-        return int(lib().fftconv_matrix_lookahead_period())
 
     @property
     def near_parts(self) -> int:
@@ -812,22 +879,8 @@ class MatrixLookaheadConvolver(_Base):
         """Workgroups sharing one output's far sum (0: no far rows, active <= Q)."""
         return int(lib().fftconv_matrix_lookahead_far_parts(self._h))
 
-    def set_windows(self, on: bool):
-        """off: every output sums its far rows in full on every block (the same bits)."""
-        _check(lib().fftconv_matrix_lookahead_set_windows(self._h, 1 if on else 0))
 
-    def anchors(self) -> int:
-        """Outputs that anchor when the next block starts."""
-        return int(lib().fftconv_matrix_lookahead_anchors(self._h))
-
-    def state(self):
-        """(current, active_seg_count, input_buffer_fill) of the whole matrix."""
-        out = (C.c_size_t * 3)()
-        _check(lib().fftconv_matrix_lookahead_state(self._h, out))
-        return tuple(int(v) for v in out)
-
-
-class SparseMatrixConvolver(_UpdatePairs, _Base):
+class SparseMatrixConvolver(_ListedMatrix):
     """Matrix convolution over a listed pair set (fftconv.h,
     "SparseMatrixConvolver"): one FFTConvolver instance per listed (output,
     input) pair, in lockstep; output o is the sum of the instances listed for
@@ -836,159 +889,18 @@ class SparseMatrixConvolver(_UpdatePairs, _Base):
 
     _prefix = "matrix_sparse"
 
-    def __init__(self, h, inputs: int, outputs: int, pairs: int, pair_list=None):
-        super().__init__(h, inputs)
-        self.inputs = inputs
-        self.outputs = outputs
-        self.pairs = pairs
-        self._pair_list = [(int(o), int(i)) for o, i in pair_list] if pair_list is not None else None
-
-    def _rows(self, responses):
-        r = _f32(responses)
-        if r.ndim != 2 or r.shape[0] != self.pairs:
-            raise ValueError("responses must be [pairs][len]")
-        return r
-
-    @classmethod
-    def init(cls, pairs, responses, inputs: int, outputs: int, max_block_size: int, max_response_length: int,
-             device: int = 0):
-        """pairs: (output, input) tuples, strictly ascending; responses[n] is
-        the response of pairs[n]."""
-        pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
-        if pr.size and (pr.min() < 0 or pr.max() >= 1 << 32):
-            raise ValueError("pair indices must fit 32 unsigned bits")
-        po = np.ascontiguousarray(pr[:, 0].astype(np.uint32))
-        pi = np.ascontiguousarray(pr[:, 1].astype(np.uint32))
-        r = _f32(responses)
-        if r.ndim != 2 or r.shape[0] != len(pr):
-            raise ValueError("responses must be [pairs][len]")
-        n = r.shape[1]
-        h = lib().fftconv_matrix_sparse_init(device, inputs, outputs, len(pr), po.ctypes.data_as(_u32p),
-                                             pi.ctypes.data_as(_u32p), _p(r), n, n, max_block_size,
-                                             max_response_length)
-        return cls(_handle(h), inputs, outputs, len(pr), pr.tolist())
-
-    def update(self, responses):
-        """update() of every listed pair with responses[pairs][len] (whole matrix only)."""
-        r = self._rows(responses)
-        _check(lib().fftconv_matrix_sparse_update(self._h, _p(r), r.shape[1], r.shape[1]))
-
-    def update_device(self, d_responses: int, response_len: int, stride: int = 0, stream: int = 0):
-        """update() from device memory (pair n, in list order, at d_responses +
-        4 * n * stride; stride 0 = one response for every pair), stream-ordered."""
-        _check(self._fn("update_device")(self._h, C.c_void_p(d_responses), response_len, stride,
-                                         C.c_void_p(stream) if stream else None))
-
-    def reset(self):
-        _check(lib().fftconv_matrix_sparse_reset(self._h))
-
-    def process(self, inp, out_len: int | None = None) -> np.ndarray:
-        """x[inputs][n] -> y[outputs][out_len or n]."""
-        x = _f32(inp)
-        if x.ndim != 2 or x.shape[0] != self.inputs:
-            raise ValueError(f"input must be [{self.inputs}][n]")
-        n_in = x.shape[1]
-        n = n_in if out_len is None else out_len
-        y = np.zeros((self.outputs, n), np.float32)
-        _check(lib().fftconv_matrix_sparse_process(self._h, _p(x), n_in, _p(y), n))
-        return y
-
-    def clone(self):
-        return SparseMatrixConvolver(_handle(lib().fftconv_matrix_sparse_clone(self._h)), self.inputs, self.outputs,
-                                     self.pairs, self._pair_list)
-
-    @property
-    def block_size(self) -> int:
-        return int(lib().fftconv_matrix_sparse_block_size(self._h))
-
-    @property
-    def seg_count(self) -> int:
-        return int(lib().fftconv_matrix_sparse_seg_count(self._h))
-
     def output_parts(self, o: int) -> int:
         """P_o: workgroups sharing output o's spectral sum, for the current active_seg_count."""
         return int(lib().fftconv_matrix_sparse_output_parts(self._h, o))
 
-    def state(self):
-        """(current, active_seg_count, input_buffer_fill) of the whole matrix."""
-        out = (C.c_size_t * 3)()
-        _check(lib().fftconv_matrix_sparse_state(self._h, out))
-        return tuple(int(v) for v in out)
 
-
-class SparseMatrixLookaheadConvolver(_UpdatePairs, _Base):
+class SparseMatrixLookaheadConvolver(_MatrixWindows, _ListedMatrix):
     """The SparseMatrixConvolver with the MatrixLookaheadConvolver's far-row
     windows (fftconv.h, "SparseMatrixLookaheadConvolver"): one FFTConvolver
     instance per listed (output, input) pair, an output's rows s >= period summed
     once every `period` blocks for the next `period` blocks.  Blocks 32..512."""
 
     _prefix = "matrix_sparse_lookahead"
-
-    def __init__(self, h, inputs: int, outputs: int, pairs: int, pair_list=None):
-        super().__init__(h, inputs)
-        self.inputs = inputs
-        self.outputs = outputs
-        self.pairs = pairs
-        self._pair_list = [(int(o), int(i)) for o, i in pair_list] if pair_list is not None else None
-
-    @classmethod
-    def init(cls, pairs, responses, inputs: int, outputs: int, max_block_size: int, max_response_length: int,
-             device: int = 0):
-        """pairs: (output, input) tuples, strictly ascending; responses[n] is
-        the response of pairs[n]."""
-        po, pi = _pair_arrays(pairs)
-        r = _f32(responses)
-        if r.ndim != 2 or r.shape[0] != len(po):
-            raise ValueError("responses must be [pairs][len]")
-        n = r.shape[1]
-        h = lib().fftconv_matrix_sparse_lookahead_init(device, inputs, outputs, len(po), po.ctypes.data_as(_u32p),
-                                                       pi.ctypes.data_as(_u32p), _p(r), n, n, max_block_size,
-                                                       max_response_length)
-        return cls(_handle(h), inputs, outputs, len(po), list(zip(po.tolist(), pi.tolist())))
-
-    def update(self, responses):
-        """update() of every listed pair with responses[pairs][len]."""
-        r = _f32(responses)
-        if r.ndim != 2 or r.shape[0] != self.pairs:
-            raise ValueError("responses must be [pairs][len]")
-        _check(self._fn("update")(self._h, _p(r), r.shape[1], r.shape[1]))
-
-    def update_device(self, d_responses: int, response_len: int, stride: int = 0, stream: int = 0):
-        """update() from device memory (pair n, in list order, at d_responses +
-        4 * n * stride; stride 0 = one response for every pair), stream-ordered."""
-        _check(self._fn("update_device")(self._h, C.c_void_p(d_responses), response_len, stride,
-                                         C.c_void_p(stream) if stream else None))
-
-    def reset(self):
-        _check(self._fn("reset")(self._h))
-
-    def process(self, inp, out_len: int | None = None) -> np.ndarray:
-        """x[inputs][n] -> y[outputs][out_len or n]."""
-        x = _f32(inp)
-        if x.ndim != 2 or x.shape[0] != self.inputs:
-            raise ValueError(f"input must be [{self.inputs}][n]")
-        n_in = x.shape[1]
-        n = n_in if out_len is None else out_len
-        y = np.zeros((self.outputs, n), np.float32)
-        _check(self._fn("process")(self._h, _p(x), n_in, _p(y), n))
-        return y
-
-    def clone(self):
-        return SparseMatrixLookaheadConvolver(_handle(self._fn("clone")(self._h)), self.inputs, self.outputs,
-                                              self.pairs, self._pair_list)
-
-    @property
-    def block_size(self) -> int:
-        return int(self._fn("block_size")(self._h))
-
-    @property
-    def seg_count(self) -> int:
-        return int(self._fn("seg_count")(self._h))
-
-    @staticmethod
-    def period() -> int:
-        """Q, the MatrixLookaheadConvolver's."""
-        return int(lib().fftconv_matrix_lookahead_period())
 
     def near_parts(self, o: int) -> int:
         """Pn_o: workgroups sharing output o's near sum, for the current active_seg_count."""
@@ -998,22 +910,8 @@ class SparseMatrixLookaheadConvolver(_UpdatePairs, _Base):
         """Pf_o: workgroups sharing output o's far sum (0: no far rows or no pairs)."""
         return int(self._fn("far_parts")(self._h, o))
 
-    def set_windows(self, on: bool):
-        """off: every output sums its far rows in full on every block (the same bits)."""
-        _check(self._fn("set_windows")(self._h, 1 if on else 0))
 
-    def anchors(self) -> int:
-        """Outputs with at least one pair that anchor when the next block starts."""
-        return int(self._fn("anchors")(self._h))
-
-    def state(self):
-        """(current, active_seg_count, input_buffer_fill) of the whole matrix."""
-        out = (C.c_size_t * 3)()
-        _check(self._fn("state")(self._h, out))
-        return tuple(int(v) for v in out)
-
-
-class MatrixCrossfadeConvolver(_UpdatePairs, _Base):
+class MatrixCrossfadeConvolver(_MatrixCrossfade, _MatrixBase):
     """Crossfaded response switching for the matrix (fftconv.h,
     "MatrixCrossfadeConvolver"): inputs x outputs CrossfadeConvolver<FFTConvolver>
     instances in lockstep, one crossfader, the mix applied to the per-output sums."""
@@ -1021,16 +919,20 @@ class MatrixCrossfadeConvolver(_UpdatePairs, _Base):
     _prefix = "matrix_crossfade"
 
     def __init__(self, h, inputs: int, outputs: int, max_buffer_size: int):
-        super().__init__(h, inputs)
-        self.inputs = inputs
-        self.outputs = outputs
+        super().__init__(h, inputs, outputs)
         self.max_buffer_size = max_buffer_size
+
+    def _clone_args(self):
+        return self.inputs, self.outputs, self.max_buffer_size
+
+    def _all_pairs(self):
+        return [(o, i) for o in range(self.outputs) for i in range(self.inputs)]
 
     @classmethod
     def init(cls, responses, max_block_size: int, max_response_length: int, device: int = 0):
         """Convolution::init (:46-49) over responses[O][I][len]: the fade takes
         len samples, the hold min(max_block_size, len)."""
-        r = MatrixConvolver._pairs(responses)
+        r = _dense_responses(responses)
         O, I, n = r.shape
         h = lib().fftconv_matrix_crossfade_init(device, I, O, _p(r), n, n, max_block_size, max_response_length)
         return cls(_handle(h), I, O, max_block_size)
@@ -1043,69 +945,8 @@ class MatrixCrossfadeConvolver(_UpdatePairs, _Base):
         h = lib().fftconv_matrix_crossfade_new(convolver._h, max_response_length, max_buffer_size, crossfade_samples)
         return cls(_handle(h), convolver.inputs, convolver.outputs, max_buffer_size)
 
-    def update(self, responses):
-        """update() of every pair with responses[O][I][len] (:51-64): starts the
-        fade, or is stored until the fade under way has ended."""
-        r = MatrixConvolver._pairs(responses, self.inputs, self.outputs)
-        _check(lib().fftconv_matrix_crossfade_update(self._h, _p(r), r.shape[2], r.shape[2]))
 
-    def update_device(self, d_responses: int, response_len: int, stride: int = 0, stream: int = 0):
-        """update() from device memory (pair o * inputs + i at d_responses +
-        4 * pair * stride; stride 0 = one response for every pair), stream-ordered."""
-        _check(self._fn("update_device")(self._h, C.c_void_p(d_responses), response_len, stride,
-                                         C.c_void_p(stream) if stream else None))
-
-    def update_input(self, i: int, responses):
-        """update_pairs of every pair that reads input i: responses[O][len]."""
-        self.update_pairs([(o, i) for o in range(self.outputs)], responses)
-
-    def update_output(self, o: int, responses):
-        """update_pairs of every pair that feeds output o: responses[I][len]."""
-        self.update_pairs([(o, i) for i in range(self.inputs)], responses)
-
-    def diff_pairs(self) -> int:
-        """|D|: the pairs whose spectra may differ between the two convolvers."""
-        return int(lib().fftconv_matrix_crossfade_diff_pairs(self._h))
-
-    def last_patch(self):
-        """(pairs transformed, pairs copied) by the last applied swap."""
-        out = (C.c_size_t * 2)()
-        _check(lib().fftconv_matrix_crossfade_last_patch(self._h, out))
-        return tuple(int(v) for v in out)
-
-    def reset(self):
-        _check(lib().fftconv_matrix_crossfade_reset(self._h))
-
-    def process(self, inp, out_len: int | None = None) -> np.ndarray:
-        """x[inputs][n >= max_buffer_size] -> y[outputs][out_len or n]; the state
-        advances by max_buffer_size samples whatever out_len is."""
-        x = _f32(inp)
-        if x.ndim != 2 or x.shape[0] != self.inputs:
-            raise ValueError(f"input must be [{self.inputs}][n]")
-        n_in = x.shape[1]
-        n = n_in if out_len is None else out_len
-        y = np.zeros((self.outputs, n), np.float32)
-        _check(lib().fftconv_matrix_crossfade_process(self._h, _p(x), n_in, _p(y), n))
-        return y
-
-    def is_crossfading(self) -> bool:
-        return bool(lib().fftconv_matrix_crossfade_is_crossfading(self._h))
-
-    def clone(self):
-        return MatrixCrossfadeConvolver(_handle(lib().fftconv_matrix_crossfade_clone(self._h)), self.inputs,
-                                        self.outputs, self.max_buffer_size)
-
-    def set_fused(self, on: bool):
-        """False: every call takes the composition path (tests, A/B runs)."""
-        _check(lib().fftconv_matrix_crossfade_set_fused(self._h, 1 if on else 0))
-
-    def path(self) -> int:
-        """The path the next process() takes: 0 composition, 1 fused with both
-        convolvers live, 2 fused with one convolver idle."""
-        return int(lib().fftconv_matrix_crossfade_path(self._h))
-
-
-class SparseMatrixCrossfadeConvolver(_UpdatePairs, _Base):
+class SparseMatrixCrossfadeConvolver(_MatrixCrossfade, _MatrixBase):
     """Crossfaded response switching for the sparse matrix (fftconv.h,
     "SparseMatrixCrossfadeConvolver"): one CrossfadeConvolver<FFTConvolver>
     instance per listed (output, input) pair, in lockstep, one crossfader, the
@@ -1114,18 +955,15 @@ class SparseMatrixCrossfadeConvolver(_UpdatePairs, _Base):
     _prefix = "matrix_sparse_crossfade"
 
     def __init__(self, h, inputs: int, outputs: int, pair_list, max_buffer_size: int):
-        super().__init__(h, inputs)
-        self.inputs = inputs
-        self.outputs = outputs
-        self._pair_list = [(int(o), int(i)) for o, i in pair_list]
-        self.pairs = len(self._pair_list)
+        super().__init__(h, inputs, outputs)
+        self._set_pair_list(pair_list)
         self.max_buffer_size = max_buffer_size
 
-    def _rows(self, responses):
-        r = _f32(responses)
-        if r.ndim != 2 or r.shape[0] != self.pairs:
-            raise ValueError("responses must be [pairs][len]")
-        return r
+    def _clone_args(self):
+        return self.inputs, self.outputs, self._pair_list, self.max_buffer_size
+
+    def _all_pairs(self):
+        return self._pair_list
 
     @classmethod
     def init(cls, pairs, responses, inputs: int, outputs: int, max_block_size: int, max_response_length: int,
@@ -1134,9 +972,7 @@ class SparseMatrixCrossfadeConvolver(_UpdatePairs, _Base):
         tuples, strictly ascending; responses[n] is the response of pairs[n]):
         the fade takes len samples, the hold min(max_block_size, len)."""
         po, pi = _pair_arrays(pairs)
-        r = _f32(responses)
-        if r.ndim != 2 or r.shape[0] != len(po):
-            raise ValueError("responses must be [pairs][len]")
+        r = _listed_responses(responses, len(po))
         n = r.shape[1]
         h = lib().fftconv_matrix_sparse_crossfade_init(device, inputs, outputs, len(po), po.ctypes.data_as(_u32p),
                                                        pi.ctypes.data_as(_u32p), _p(r), n, n, max_block_size,
@@ -1152,67 +988,6 @@ class SparseMatrixCrossfadeConvolver(_UpdatePairs, _Base):
         h = lib().fftconv_matrix_sparse_crossfade_new(convolver._h, max_response_length, max_buffer_size,
                                                       crossfade_samples)
         return cls(_handle(h), convolver.inputs, convolver.outputs, convolver._pair_list, max_buffer_size)
-
-    def update(self, responses):
-        """update() of every listed pair with responses[pairs][len] (:51-64):
-        starts the fade, or is stored until the fade under way has ended."""
-        r = self._rows(responses)
-        _check(lib().fftconv_matrix_sparse_crossfade_update(self._h, _p(r), r.shape[1], r.shape[1]))
-
-    def update_device(self, d_responses: int, response_len: int, stride: int = 0, stream: int = 0):
-        """update() from device memory (pair n, in list order, at d_responses +
-        4 * n * stride; stride 0 = one response for every pair), stream-ordered."""
-        _check(self._fn("update_device")(self._h, C.c_void_p(d_responses), response_len, stride,
-                                         C.c_void_p(stream) if stream else None))
-
-    def update_input(self, i: int, responses):
-        """update_pairs of the listed pairs that read input i, in list order."""
-        self.update_pairs([p for p in self._pair_list if p[1] == i], responses)
-
-    def update_output(self, o: int, responses):
-        """update_pairs of the listed pairs that feed output o, in list order."""
-        self.update_pairs([p for p in self._pair_list if p[0] == o], responses)
-
-    def diff_pairs(self) -> int:
-        """|D|: the listed pairs whose spectra may differ between the two convolvers."""
-        return int(lib().fftconv_matrix_sparse_crossfade_diff_pairs(self._h))
-
-    def last_patch(self):
-        """(pairs transformed, pairs copied) by the last applied swap."""
-        out = (C.c_size_t * 2)()
-        _check(lib().fftconv_matrix_sparse_crossfade_last_patch(self._h, out))
-        return tuple(int(v) for v in out)
-
-    def reset(self):
-        _check(lib().fftconv_matrix_sparse_crossfade_reset(self._h))
-
-    def process(self, inp, out_len: int | None = None) -> np.ndarray:
-        """x[inputs][n >= max_buffer_size] -> y[outputs][out_len or n]; the state
-        advances by max_buffer_size samples whatever out_len is."""
-        x = _f32(inp)
-        if x.ndim != 2 or x.shape[0] != self.inputs:
-            raise ValueError(f"input must be [{self.inputs}][n]")
-        n_in = x.shape[1]
-        n = n_in if out_len is None else out_len
-        y = np.zeros((self.outputs, n), np.float32)
-        _check(lib().fftconv_matrix_sparse_crossfade_process(self._h, _p(x), n_in, _p(y), n))
-        return y
-
-    def is_crossfading(self) -> bool:
-        return bool(lib().fftconv_matrix_sparse_crossfade_is_crossfading(self._h))
-
-    def clone(self):
-        return SparseMatrixCrossfadeConvolver(_handle(lib().fftconv_matrix_sparse_crossfade_clone(self._h)),
-                                              self.inputs, self.outputs, self._pair_list, self.max_buffer_size)
-
-    def set_fused(self, on: bool):
-        """False: every call takes the composition path (tests, A/B runs)."""
-        _check(lib().fftconv_matrix_sparse_crossfade_set_fused(self._h, 1 if on else 0))
-
-    def path(self) -> int:
-        """The path the next process() takes: 0 composition, 1 fused with both
-        convolvers live, 2 fused with one convolver idle."""
-        return int(lib().fftconv_matrix_sparse_crossfade_path(self._h))
 
 
 class MatrixTwoStageConvolver(_Base):
@@ -1231,7 +1006,7 @@ class MatrixTwoStageConvolver(_Base):
     @classmethod
     def init(cls, responses, max_block_size: int, max_response_length: int, device: int = 0):
         """responses[O][I][len]: h[o][i] is the response from input i to output o."""
-        r = MatrixConvolver._pairs(responses)
+        r = _dense_responses(responses)
         O, I, n = r.shape
         h = lib().fftconv_matrix_twostage_init(device, I, O, _p(r), n, n, max_block_size, max_response_length)
         return cls(_handle(h), I, O)
@@ -1239,7 +1014,7 @@ class MatrixTwoStageConvolver(_Base):
     def update(self, responses):
         """todo!() in the reference (src/fft_convolver.rs:408-410): raises
         NotImplementedInReference, the handle is unchanged."""
-        r = MatrixConvolver._pairs(responses, self.inputs, self.outputs)
+        r = _dense_responses(responses, self.inputs, self.outputs)
         _check(lib().fftconv_matrix_twostage_update(self._h, _p(r), r.shape[2], r.shape[2]))
 
     def reset(self):

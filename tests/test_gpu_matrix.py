@@ -455,3 +455,111 @@ def test_nontemporal_instantiation(amd, s):
         _check_ref(y, ref, f"{what} {shape_id(s)}")
         assert np.abs(y).max() > 0
     assert np.array_equal(ys[0], ys[1])
+
+
+# ---- the host paths every matrix handle type shares -------------------------
+_SH_I, _SH_O, _SH_B, _SH_L, _SH_N = 2, 3, 32, 100, 20  # calls of 20 samples: every call ends mid-block
+_SH_PAIRS = [(o, i) for o in range(_SH_O) for i in range(_SH_I)]  # the full pattern, in the dense order
+
+
+def _shared_handle(amd, kind, h):
+    rows = h.reshape(_SH_O * _SH_I, -1)
+    dense = lambda: amd.MatrixConvolver.init(h, _SH_B, _SH_L)
+    sparse = lambda: amd.SparseMatrixConvolver.init(_SH_PAIRS, rows, _SH_I, _SH_O, _SH_B, _SH_L)
+    if kind == "matrix":
+        return dense()
+    if kind == "matrix_sparse":
+        return sparse()
+    if kind == "matrix_lookahead":
+        return amd.MatrixLookaheadConvolver.init(h, _SH_B, _SH_L)
+    if kind == "matrix_sparse_lookahead":
+        return amd.SparseMatrixLookaheadConvolver.init(_SH_PAIRS, rows, _SH_I, _SH_O, _SH_B, _SH_L)
+    if kind == "matrix_crossfade":  # max_buffer_size 20: the two convolvers' blocks end inside a call
+        return amd.MatrixCrossfadeConvolver.new(dense(), _SH_L, _SH_N, _SH_L)
+    if kind == "matrix_sparse_crossfade":
+        return amd.SparseMatrixCrossfadeConvolver.new(sparse(), _SH_L, _SH_N, _SH_L)
+    assert kind == "matrix_twostage"
+    return amd.MatrixTwoStageConvolver.init(h, _SH_B, _SH_L)
+
+
+@functools.lru_cache(maxsize=None)
+def _shared_case():
+    h, x = make(31, _SH_I, _SH_O, _SH_L, 6 * _SH_N)
+    ref = direct(oracle_module, x, h)
+    for a in (h, x, ref):
+        a.setflags(write=False)
+    return h, x, ref
+
+
+# the dense handle whose output a sparse one over the full pattern repeats bit for bit
+_SH_DENSE_OF = {"matrix_sparse": "matrix", "matrix_sparse_lookahead": "matrix_lookahead",
+                "matrix_sparse_crossfade": "matrix_crossfade"}
+
+
+@pytest.mark.parametrize("kind", ["matrix", "matrix_lookahead", "matrix_sparse", "matrix_sparse_lookahead",
+                                  "matrix_crossfade", "matrix_sparse_crossfade", "matrix_twostage"])
+def test_shared_host_paths(amd, kind):
+    """The host code all seven matrix handle types run through one definition
+    (the block walk, process(), clone, the zero-length cases), at I = 2, O = 3,
+    B = 32, IR length 100, calls of 20 samples; the sparse types over the full
+    pattern, so the dense type's output is theirs bit for bit.
+      - a zero-length process() is a no-op (not for the crossfaded types: the
+        reference advances both convolvers by max_buffer_size whatever the
+        output length is, test_gpu_matrix_xf.test_errors_and_init_form);
+      - clone() taken mid-block continues bit-identically to the original;
+      - update() to a zero-length response, then process_device: exact zeros
+        are written, the rest of the output buffer and state() are untouched
+        (the crossfaded types once the fade has ended; they and the two-stage
+        matrix have no state(), and the two-stage update is todo!() in the
+        reference: test_gpu_matrix_ts.test_errors)."""
+    h, x, ref = _shared_case()
+    n, I, O = _SH_N, _SH_I, _SH_O
+    crossfaded = kind.endswith("crossfade")
+    has_state = not crossfaded and kind != "matrix_twostage"
+    conv = _shared_handle(amd, kind, h)
+    dense = _shared_handle(amd, _SH_DENSE_OF[kind], h) if kind in _SH_DENSE_OF else None
+
+    def calls(c, first, count):
+        return np.concatenate([c.process(x[:, k * n:(k + 1) * n]) for k in range(first, first + count)], axis=1)
+
+    y0 = calls(conv, 0, 3)
+    if has_state:
+        assert conv.state() == (3, 4, 3 * n % _SH_B)  # one block completed of 4 segments, mid-block
+    if not crossfaded:
+        state = conv.state() if has_state else None
+        assert conv.process(x[:, :0]).shape == (O, 0)
+        if has_state:
+            assert conv.state() == state
+    twin = conv.clone()
+    if has_state:
+        assert twin.state() == conv.state() and conv.state()[2] != 0
+    ya = calls(conv, 3, 3)
+    yb = calls(twin, 3, 3)
+    assert np.array_equal(ya, yb), "the clone differs from the original"
+    y = np.concatenate([y0, ya], axis=1)
+    _check_outputs(y, ref, kind)
+    if dense is not None:
+        assert np.array_equal(y, calls(dense, 0, 6)), "sparse over the full pattern differs from dense"
+
+    if kind == "matrix_twostage":
+        return
+    empty = np.zeros((O * I, 0) if kind in _SH_DENSE_OF else (O, I, 0), np.float32)
+    conv.update(empty)
+    if crossfaded:
+        for _ in range(2 * _SH_L // n + 2):  # the fade of L samples and the hold, with room
+            conv.process(x[:, :n])
+        assert not conv.is_crossfading()
+    state = conv.state() if has_state else None
+    if has_state:
+        assert state[1] == 0
+    dev = torch.device("cuda:0")
+    xd = torch.ones((I, n), device=dev)
+    yd = torch.full((O, n + 3), -7.0, device=dev)
+    conv.process_device(xd.data_ptr(), n, yd.data_ptr(), n + 3, n)
+    conv.synchronize()
+    torch.cuda.synchronize()
+    out = yd.cpu().numpy()
+    assert (out[:, :n] == 0.0).all()
+    assert (out[:, n:] == -7.0).all()
+    if has_state:
+        assert conv.state() == state
