@@ -2270,6 +2270,7 @@ struct MatrixBase : BlockWalk {
 struct MatrixCore : MatrixBase<MatrixCore> {
     static constexpr const char *kName = "matrix";
     using XfArgs = MatrixXfArgs;
+    using TsArgs = MatrixTsArgs;
     size_t Pmax = 1;      // MAC parts at active = S (the `part` rows per output)
 
     int mac_parts() const { return matrix_mac_parts((int)I, log2b, (int)S, (int)act); }
@@ -2328,6 +2329,14 @@ struct MatrixCore : MatrixBase<MatrixCore> {
         x.rpp = (int)ceil_div(I * (act - 1), (size_t)x.P);
     }
     static hipError_t launch_xf_chunk(int log2b, const XfArgs &x, hipStream_t s) { return launch_matrix_xf_chunk(log2b, x, s); }
+
+    // the fused two-stage launch (matrix_ts.hip), this matrix being the head
+    void ts_args(TsArgs &x) const {
+        x.P = mac_parts();
+        x.rpp = (int)ceil_div(I * (act - 1), (size_t)x.P);
+    }
+    bool ts_plan_equal(const MatrixCore &) const { return true; }  // (the MAC grid is a function of {I, S, active})
+    static hipError_t launch_ts_block(int log2b, const TsArgs &x, hipStream_t s) { return launch_matrix_ts_block(log2b, x, s); }
 
     int clone_from(const MatrixCore &o, hipStream_t owner = nullptr) {  // #[derive(Clone)]
         DeviceGuard g(o.device);
@@ -2446,6 +2455,7 @@ struct MatrixLookaheadCore {
 struct SparseMatrixCore : MatrixBase<SparseMatrixCore> {
     static constexpr const char *kName = "sparse matrix";
     using XfArgs = MatrixSpXfArgs;
+    using TsArgs = MatrixSpTsArgs;
     size_t PTmax = 0;     // sum of P_o at active = S (the rows of `part`)
     size_t PT = 0;        // sum of P_o at the current active
     std::vector<int> rowptr, col;  // the host's copy of the pattern
@@ -2495,13 +2505,14 @@ struct SparseMatrixCore : MatrixBase<SparseMatrixCore> {
         return e ? pair_list_error(e) : FFTCONV_OK;
     }
 
-    int alloc_geometry(int dev, size_t inputs, size_t outputs, size_t pairs, size_t max_block_size, size_t max_len) {
+    int alloc_geometry(int dev, size_t inputs, size_t outputs, size_t pairs, size_t max_block_size, size_t max_len,
+                       hipStream_t owner) {
         if (int r = set_geometry(dev, inputs, outputs, pairs, max_block_size, max_len)) return r;
         if (P * std::max<size_t>(S, 1) > (size_t)INT32_MAX)
             return fail(FFTCONV_E_UNSUPPORTED, "geometry exceeds 32-bit indexing");
         PTmax = total_parts(S);
         if (I + PTmax > (size_t)INT32_MAX) return fail(FFTCONV_E_UNSUPPORTED, "geometry exceeds 32-bit indexing");
-        if (int r = alloc_walk(nullptr, PTmax)) return r;          // (P_o is largest at active = S)
+        if (int r = alloc_walk(owner, PTmax)) return r;            // (P_o is largest at active = S)
         if (int r = d_rowptr.alloc(O + 1)) return r;
         if (int r = d_col.alloc(P)) return r;
         if (int r = plan.alloc(O + 1)) return r;
@@ -2512,8 +2523,10 @@ struct SparseMatrixCore : MatrixBase<SparseMatrixCore> {
         return FFTCONV_OK;
     }
 
+    // `owner`: the matrix is a stage of a SparseMatrixTwoStageCore and runs on that stream
     int init(int dev, size_t inputs, size_t outputs, size_t pairs, const uint32_t *po, const uint32_t *pi,
-             const float *responses, size_t len, size_t stride, size_t max_block, size_t max_len) {
+             const float *responses, size_t len, size_t stride, size_t max_block, size_t max_len,
+             hipStream_t owner = nullptr) {
         if (int r = check_pattern(inputs, outputs, pairs, po, pi)) return r;
         if (max_len < len)                                          // :106-110
             return fail(FFTCONV_E_INVALID,
@@ -2527,7 +2540,7 @@ struct SparseMatrixCore : MatrixBase<SparseMatrixCore> {
         }
         for (size_t o = 0; o < outputs; ++o) rowptr[o + 1] += rowptr[o];
         DeviceGuard g(dev);
-        if (int r = alloc_geometry(dev, inputs, outputs, pairs, max_block, max_len)) return r;
+        if (int r = alloc_geometry(dev, inputs, outputs, pairs, max_block, max_len, owner)) return r;
         if (int r = zero_state(stream)) return r;
         if (int r = rebuild_plan(stream)) return r;
         return init_responses(responses, len, stride);
@@ -2560,6 +2573,17 @@ struct SparseMatrixCore : MatrixBase<SparseMatrixCore> {
         x.PT = (int)PT;
     }
     static hipError_t launch_xf_chunk(int log2b, const XfArgs &x, hipStream_t s) { return launch_matrix_sp_xf_chunk(log2b, x, s); }
+
+    // the fused two-stage launch (matrix_sp_ts.hip), this matrix being the
+    // head.  Head and tail0 hold the same pattern, so equal {S, active} give
+    // equal plans; the part counts are compared all the same.
+    void ts_args(TsArgs &x) const {
+        x.rowptr = d_rowptr.p; x.col = d_col.p; x.plan = plan.p; x.wg = wg.p;
+        x.N = (int)P;
+        x.PT = (int)PT;
+    }
+    bool ts_plan_equal(const SparseMatrixCore &t) const { return PT == t.PT; }
+    static hipError_t launch_ts_block(int log2b, const TsArgs &x, hipStream_t s) { return launch_matrix_sp_ts_block(log2b, x, s); }
 
     int clone_from(const SparseMatrixCore &o, hipStream_t owner = nullptr) {  // #[derive(Clone)]
         DeviceGuard g(o.device);
@@ -3175,33 +3199,39 @@ using SparseMatrixCrossfadeCore = MatrixCrossfadeCoreT<SparseMatrixCore>;
 
 
 // ---------------------------------------------------------------------------
-// MatrixTwoStageCore -- I x O TwoStageFFTConvolver instances (o, i) in lockstep
-// (DESIGN §4k): up to three MatrixCores (head, tail0, tail) on the handle's
-// stream, ONE {tail_input_fill, precalculated_pos} for all of them, the four
-// tail buffers summed per output [O][T], tail_input per input [I][T].
+// MatrixTwoStageCoreT -- P TwoStageFFTConvolver instances in lockstep, one per
+// pair of the matrix Conv (the dense matrix's O * I pairs; §4r: the
+// N listed pairs of a sparse pattern): up to three Convs (head, tail0, tail) on
+// the handle's stream, ONE {tail_input_fill, precalculated_pos} for all of
+// them, the four tail buffers summed per output [O][T], tail_input per input
+// [I][T].
 //   composition path: TwoStageCore::process_device's sub-chunk loop
 //       (src/fft_convolver.rs:412-495) with matrices for convolvers (always
 //       correct)
-//   fused path (matrix_ts.hip), at an aligned call: head, the sub-chunk's sums
-//       and copy, and tail0 in the plain matrix's two launches, every delay-
-//       line row streamed once for both responses.  Head and tail0 count
-//       samples modulo B from the same start, so at an aligned call their last
-//       S rows are transforms of the same input blocks whatever ragged calls
-//       came before.
+//   fused path (matrix_ts.hip / matrix_sp_ts.hip), at an aligned call: head, the
+//       sub-chunk's sums and copy, and tail0 in the plain matrix's two launches,
+//       every delay-line row streamed once for both responses.  Head and tail0
+//       count samples modulo B from the same start, so at an aligned call their
+//       last S rows are transforms of the same input blocks whatever ragged
+//       calls came before.
 // Everything is enqueued on one stream in stream order; the tail's block-T
 // convolution at the end of a period is enqueued inline, where the reference
 // runs it (:479-486).
+// Conv supplies kName, init / clone_from with an owner stream, and the fused
+// launch: TsArgs, ts_args, ts_plan_equal (head and tail0 walk the same MAC
+// grid), launch_ts_block.
 // ---------------------------------------------------------------------------
-struct MatrixTwoStageCore {
+template <class Conv>
+struct MatrixTwoStageCoreT {
     int device = 0;
-    size_t I = 0, O = 0, head_bs = 0, T = 0;
-    std::unique_ptr<MatrixCore> head, tail0, tail;  // null = the reference's Default convolver (zeros): skipped
+    size_t I = 0, O = 0, P = 0, head_bs = 0, T = 0;  // P: pairs
+    std::unique_ptr<Conv> head, tail0, tail;  // null = the reference's Default convolver (zeros): skipped
     DevPtr<float> out0, pre0, out1, pre1;           // [O][T] each
     DevPtr<float> tin;                              // tail_input [I][T]
     float *tail_output0 = nullptr, *tail_precalculated0 = nullptr;
     float *tail_output = nullptr, *tail_precalculated = nullptr;
     size_t tail_input_fill = 0, precalculated_pos = 0;
-    bool fused = true;  // fftconv_matrix_twostage_set_fused
+    bool fused = true;  // fftconv_matrix[_sparse]_twostage_set_fused
     // a launch failed inside a call: the stages may be out of step with the
     // host's scalars.  Every later call fails.
     bool poisoned = false;
@@ -3209,7 +3239,7 @@ struct MatrixTwoStageCore {
     Scratch scratch;
     mutable StreamOrder order;
 
-    ~MatrixTwoStageCore() {
+    ~MatrixTwoStageCoreT() {
         if (stream) {
             DeviceGuard g(device);
             (void)order.drain(stream);
@@ -3219,8 +3249,8 @@ struct MatrixTwoStageCore {
     }
 
     int check_poisoned() const {
-        return poisoned ? fail(FFTCONV_E_DEVICE, "matrix two-stage handle unusable: an earlier process() failed "
-                                                  "between its stages' launches")
+        return poisoned ? fail(FFTCONV_E_DEVICE, std::string(Conv::kName) + " two-stage handle unusable: an earlier "
+                                                                            "process() failed between its stages' launches")
                         : FFTCONV_OK;
     }
 
@@ -3236,10 +3266,30 @@ struct MatrixTwoStageCore {
         return FFTCONV_OK;
     }
 
-    // TwoStageFFTConvolver::init (:340-406) of every instance
+    // TwoStageFFTConvolver::init (:340-406) of every instance.  The dense
+    // matrix: pair (o, i) = o * I + i.
     int init(int dev, size_t inputs, size_t outputs, const float *responses, size_t len, size_t stride,
              size_t block_size, size_t max_len) {
         if (inputs == 0 || outputs == 0) return fail(FFTCONV_E_INVALID, "a matrix needs at least one input and one output");
+        return init_stages(dev, inputs, outputs, inputs * outputs, responses, len, stride, block_size, max_len,
+                           [&](Conv &m, const float *rows, size_t cnt, size_t row_stride, size_t block) {
+                               return m.init(dev, I, O, rows, cnt, row_stride, block, cnt, stream);
+                           });
+    }
+    // The sparse matrix: the listed pairs, responses in list order.
+    int init(int dev, size_t inputs, size_t outputs, size_t pairs, const uint32_t *po, const uint32_t *pi,
+             const float *responses, size_t len, size_t stride, size_t block_size, size_t max_len) {
+        if (int r = Conv::check_pattern(inputs, outputs, pairs, po, pi)) return r;
+        return init_stages(dev, inputs, outputs, pairs, responses, len, stride, block_size, max_len,
+                           [&](Conv &m, const float *rows, size_t cnt, size_t row_stride, size_t block) {
+                               return m.init(dev, I, O, pairs, po, pi, rows, cnt, row_stride, block, cnt, stream);
+                           });
+    }
+
+    // `stage_init(m, rows, cnt, row_stride, block)`: Conv::init of one stage from its slices
+    template <class StageInit>
+    int init_stages(int dev, size_t inputs, size_t outputs, size_t pairs, const float *responses, size_t len,
+                    size_t stride, size_t block_size, size_t max_len, StageInit stage_init) {
         if (max_len < len)                                                      // :344-348
             return fail(FFTCONV_E_INVALID,
                         "max_response_length must be at least the length of the initial impulse response");
@@ -3256,21 +3306,22 @@ struct MatrixTwoStageCore {
         device = dev;
         I = inputs;
         O = outputs;
+        P = pairs;
         DeviceGuard g(dev);
         HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         // padded_ir = each pair's response zero-extended to max_len (:349-350);
-        // the sub-ranges are cut on the host, so each stage sees its reference slice
-        const size_t pairs = O * I;
+        // the sub-ranges are cut on the host, one row per pair, so each stage
+        // sees its reference slice
         const bool shared = stride == 0 && pairs > 1;
         std::vector<float> tmp;
-        auto stage = [&](std::unique_ptr<MatrixCore> &m, size_t off, size_t cnt, size_t block) -> int {
+        auto stage = [&](std::unique_ptr<Conv> &m, size_t off, size_t cnt, size_t block) -> int {
             const size_t rows = shared ? 1 : pairs;
             tmp.assign(rows * std::max<size_t>(cnt, 1), 0.f);
             for (size_t p = 0; p < rows; ++p)
                 for (size_t j = 0; j < cnt && off + j < len; ++j) tmp[p * cnt + j] = responses[p * stride + off + j];
-            m.reset(new (std::nothrow) MatrixCore());
+            m.reset(new (std::nothrow) Conv());
             if (!m) return fail(FFTCONV_E_NOMEM, "out of host memory");
-            return m->init(dev, I, O, tmp.data(), cnt, shared ? 0 : cnt, block, cnt, stream);
+            return stage_init(*m, tmp.data(), cnt, shared ? 0 : cnt, block);
         };
         if (int r = stage(head, 0, std::min(max_len, T), head_bs)) return r;             // :352-354
         if (max_len > T)                                                                  // :356-368
@@ -3289,9 +3340,10 @@ struct MatrixTwoStageCore {
     // never of `outputs`.
     int path(size_t len) const {
         if (!fused || !tail0) return 0;
-        const MatrixCore &h = *head, &t = *tail0;
+        const Conv &h = *head, &t = *tail0;
         return len == head_bs && head_bs == h.B && tail_input_fill % h.B == 0 && tail_input_fill + len <= T &&
-                       h.fill == 0 && t.fill == 0 && h.S == t.S && h.act == t.act && h.act > 0 && h.cur == t.cur
+                       h.fill == 0 && t.fill == 0 && h.S == t.S && h.act == t.act && h.act > 0 && h.cur == t.cur &&
+                       h.ts_plan_equal(t)
                    ? 1
                    : 0;
     }
@@ -3338,9 +3390,9 @@ struct MatrixTwoStageCore {
     }
 
     int process_fused(const float *din, size_t is, float *dout, size_t os, hipStream_t s) {
-        MatrixCore &h = *head, &t = *tail0;
-        MatrixTsArgs x{};
-        const MatrixCore *cv[2] = {&h, &t};
+        Conv &h = *head, &t = *tail0;
+        typename Conv::TsArgs x{};
+        const Conv *cv[2] = {&h, &t};
         for (int c = 0; c < 2; ++c) {
             x.H[c] = cv[c]->H.p; x.X[c] = cv[c]->X.p; x.ovl[c] = cv[c]->ovl.p; x.part[c] = cv[c]->part.p;
         }
@@ -3353,12 +3405,11 @@ struct MatrixTwoStageCore {
         x.p1 = tail ? tail_precalculated + precalculated_pos : nullptr;         // :448-454
         x.T = (long long)T;
         x.I = (int)I; x.O = (int)O; x.S = (int)h.S;
-        x.P = h.mac_parts();
-        x.rpp = (int)ceil_div(I * (h.act - 1), (size_t)x.P);
+        h.ts_args(x);
         x.cur = (int)h.cur;
         x.act = (int)h.act;
         x.nt_h = Variant::current().nt_matrix(h.H.bytes()) ? 1 : 0;
-        HIP_TRY(launch_matrix_ts_block(h.log2b, x, s));
+        HIP_TRY(Conv::launch_ts_block(h.log2b, x, s));
         // a whole block (:277-291 of both); the fused path is taken at h.fill == 0 only (path()),
         // so this always completes the block and steps `current`
         h.advance(h.B, h.B);
@@ -3416,15 +3467,15 @@ struct MatrixTwoStageCore {
 
     // #[derive(Clone)]: a deep device-side copy, including which buffer
     // currently plays tail_output* / tail_precalculated*
-    int clone_from(const MatrixTwoStageCore &o) {
+    int clone_from(const MatrixTwoStageCoreT &o) {
         DeviceGuard g(o.device);
         if (int r = o.order.drain(o.stream)) return r;
-        device = o.device; I = o.I; O = o.O; head_bs = o.head_bs; T = o.T;
+        device = o.device; I = o.I; O = o.O; P = o.P; head_bs = o.head_bs; T = o.T;
         fused = o.fused; poisoned = o.poisoned;
         HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        auto cl = [&](std::unique_ptr<MatrixCore> &dst, const std::unique_ptr<MatrixCore> &src) -> int {
+        auto cl = [&](std::unique_ptr<Conv> &dst, const std::unique_ptr<Conv> &src) -> int {
             if (!src) return FFTCONV_OK;
-            dst.reset(new (std::nothrow) MatrixCore());
+            dst.reset(new (std::nothrow) Conv());
             if (!dst) return fail(FFTCONV_E_NOMEM, "out of host memory");
             return dst->clone_from(*src, stream);
         };
@@ -3450,6 +3501,8 @@ struct MatrixTwoStageCore {
         return FFTCONV_OK;
     }
 };
+using MatrixTwoStageCore = MatrixTwoStageCoreT<MatrixCore>;
+using SparseMatrixTwoStageCore = MatrixTwoStageCoreT<SparseMatrixCore>;
 
 // W_N^k tables of the stand-alone Fft entry points, one per (device, N),
 // built on first use in f64 and kept for the process (the handles keep
@@ -3753,6 +3806,7 @@ struct fftconv_matrix_sparse_lookahead { SparseMatrixLookaheadCore core; };
 struct fftconv_matrix_crossfade { MatrixCrossfadeCore core; };
 struct fftconv_matrix_sparse_crossfade { SparseMatrixCrossfadeCore core; };
 struct fftconv_matrix_twostage { MatrixTwoStageCore core; };
+struct fftconv_matrix_sparse_twostage { SparseMatrixTwoStageCore core; };
 
 // The wrappers the handle types repeat, over the handle struct H (the matrix
 // handles use all of them, the others those whose shape they share).
@@ -4617,5 +4671,56 @@ int fftconv_matrix_twostage_set_fused(fftconv_matrix_twostage *h, int on) {
     return FFTCONV_OK;
 }
 int fftconv_matrix_twostage_path(const fftconv_matrix_twostage *h, size_t len) { return h ? h->core.path(len) : 0; }
+
+// ---- sparse matrix two-stage ---------------------------------------
+fftconv_matrix_sparse_twostage *fftconv_matrix_sparse_twostage_init(int device, size_t inputs, size_t outputs,
+                                                                    size_t pairs, const uint32_t *pair_out,
+                                                                    const uint32_t *pair_in, const float *responses,
+                                                                    size_t response_len, size_t response_stride,
+                                                                    size_t max_block_size, size_t max_response_length) {
+    return abi_init<fftconv_matrix_sparse_twostage>(device, inputs, outputs, pairs, pair_out, pair_in, responses,
+                                                    response_len, response_stride, max_block_size, max_response_length);
+}
+int fftconv_matrix_sparse_twostage_update(fftconv_matrix_sparse_twostage *h, const float *, size_t, size_t) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return fail(FFTCONV_E_UNIMPLEMENTED, "not yet implemented (TwoStageFFTConvolver::update is todo!())");
+}
+int fftconv_matrix_sparse_twostage_reset(fftconv_matrix_sparse_twostage *h) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.reset();
+}
+int fftconv_matrix_sparse_twostage_process(fftconv_matrix_sparse_twostage *h, const float *input, float *output,
+                                           size_t len) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    return h->core.process_host(input, output, len);
+}
+int fftconv_matrix_sparse_twostage_process_device(fftconv_matrix_sparse_twostage *h, const float *d_input,
+                                                  size_t in_stride, float *d_output, size_t out_stride, size_t len,
+                                                  void *hip_stream) {
+    return abi_process_device(h, d_input, in_stride, d_output, out_stride, len, hip_stream);
+}
+int fftconv_matrix_sparse_twostage_process_device_steps(fftconv_matrix_sparse_twostage *h, const float *d_input,
+                                                        size_t in_stride, size_t in_step, float *d_output,
+                                                        size_t out_stride, size_t out_step, size_t len, size_t steps,
+                                                        void *hip_stream) {
+    return abi_process_device_steps(h, d_input, in_stride, in_step, d_output, out_stride, out_step, len, steps, hip_stream);
+}
+fftconv_matrix_sparse_twostage *fftconv_matrix_sparse_twostage_clone(const fftconv_matrix_sparse_twostage *h) {
+    return abi_clone(h);
+}
+void fftconv_matrix_sparse_twostage_destroy(fftconv_matrix_sparse_twostage *h) { delete h; }
+int fftconv_matrix_sparse_twostage_synchronize(fftconv_matrix_sparse_twostage *h) { return abi_synchronize(h); }
+size_t fftconv_matrix_sparse_twostage_inputs(const fftconv_matrix_sparse_twostage *h) { return h ? h->core.I : 0; }
+size_t fftconv_matrix_sparse_twostage_outputs(const fftconv_matrix_sparse_twostage *h) { return h ? h->core.O : 0; }
+size_t fftconv_matrix_sparse_twostage_pairs(const fftconv_matrix_sparse_twostage *h) { return h ? h->core.P : 0; }
+size_t fftconv_matrix_sparse_twostage_tail_block_size(const fftconv_matrix_sparse_twostage *h) { return h ? h->core.T : 0; }
+int fftconv_matrix_sparse_twostage_set_fused(fftconv_matrix_sparse_twostage *h, int on) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    h->core.fused = on != 0;
+    return FFTCONV_OK;
+}
+int fftconv_matrix_sparse_twostage_path(const fftconv_matrix_sparse_twostage *h, size_t len) {
+    return h ? h->core.path(len) : 0;
+}
 
 }  // extern "C"

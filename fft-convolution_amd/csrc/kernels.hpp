@@ -643,4 +643,35 @@ struct MatrixTsAccumArgs {
 };
 hipError_t launch_matrix_ts_accum(const MatrixTsAccumArgs &a, hipStream_t s);
 
+// SparseMatrixTwoStageConvolver (matrix_sp_ts.hip): one aligned
+// call of the head [0] and tail0 [1] sparse matrices -- MatrixTsArgs over the
+// CSR pattern of MatrixSpArgs.  Head and tail0 have the same pattern and, at an
+// aligned call, the same active_seg_count, so ONE plan serves both (the head's).
+struct MatrixSpTsArgs {
+    const float2 *H[2];    // [N][S][B] each
+    float2 *X[2];          // [I][S][B] each; the block's row is written to both
+    float *ovl[2];         // [O][B]
+    float2 *part[2];       // [sum P_o][B]
+    const int *rowptr;     // as MatrixSpArgs
+    const int *col;
+    const int *plan;
+    const int4 *wg;
+    const float2 *tw;      // W_N^k, k < N = 2B
+    const float *in;       // the block of input 0 (+ in_stride per input)
+    long long in_stride;
+    float *out;            // the block of output 0 (+ out_stride per output)
+    long long out_stride;
+    float *tin;            // as MatrixTsArgs
+    float *tout0;
+    const float *p0;
+    const float *p1;
+    long long T;
+    int I, O, S, N;
+    int PT;                // plan[O]
+    int cur, act;
+    int nt_h;              // nontemporal H streams (Variant::nt_matrix of one H)
+};
+// the call's two launches (32 <= B <= 8192)
+hipError_t launch_matrix_sp_ts_block(int log2b, const MatrixSpTsArgs &a, hipStream_t s);
+
 }  // namespace fftconv

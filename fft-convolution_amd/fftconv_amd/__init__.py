@@ -237,6 +237,21 @@ SIGNATURES = {
     "fftconv_matrix_twostage_tail_block_size": (_sz, [_vp]),
     "fftconv_matrix_twostage_set_fused": (_i, [_vp, _i]),
     "fftconv_matrix_twostage_path": (_i, [_vp, _sz]),
+    "fftconv_matrix_sparse_twostage_init": (_vp, [_i, _sz, _sz, _sz, _u32p, _u32p, _fp, _sz, _sz, _sz, _sz]),
+    "fftconv_matrix_sparse_twostage_update": (_i, [_vp, _fp, _sz, _sz]),
+    "fftconv_matrix_sparse_twostage_reset": (_i, [_vp]),
+    "fftconv_matrix_sparse_twostage_process": (_i, [_vp, _fp, _fp, _sz]),
+    "fftconv_matrix_sparse_twostage_process_device": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_sparse_twostage_process_device_steps": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _sz, _sz, _vp]),
+    "fftconv_matrix_sparse_twostage_clone": (_vp, [_vp]),
+    "fftconv_matrix_sparse_twostage_destroy": (None, [_vp]),
+    "fftconv_matrix_sparse_twostage_synchronize": (_i, [_vp]),
+    "fftconv_matrix_sparse_twostage_inputs": (_sz, [_vp]),
+    "fftconv_matrix_sparse_twostage_outputs": (_sz, [_vp]),
+    "fftconv_matrix_sparse_twostage_pairs": (_sz, [_vp]),
+    "fftconv_matrix_sparse_twostage_tail_block_size": (_sz, [_vp]),
+    "fftconv_matrix_sparse_twostage_set_fused": (_i, [_vp, _i]),
+    "fftconv_matrix_sparse_twostage_path": (_i, [_vp, _sz]),
 }
 
 
@@ -1047,11 +1062,82 @@ class MatrixTwoStageConvolver(_Base):
         return int(lib().fftconv_matrix_twostage_path(self._h, n))
 
 
+class SparseMatrixTwoStageConvolver(_Base):
+    """Two-stage partitioning over a listed pair set (fftconv.h,
+    "SparseMatrixTwoStageConvolver"): one TwoStageFFTConvolver instance per
+    listed (output, input) pair, in lockstep -- head, first tail stage and tail
+    are sparse matrices over the same pattern; output o is the sum of the
+    instances listed for it, an output without pairs is zero."""
+
+    _prefix = "matrix_sparse_twostage"
+
+    def __init__(self, h, inputs: int, outputs: int, pair_list):
+        super().__init__(h, inputs)
+        self.inputs = inputs
+        self.outputs = outputs
+        self._pair_list = [(int(o), int(i)) for o, i in pair_list]
+
+    @classmethod
+    def init(cls, pairs, responses, inputs: int, outputs: int, max_block_size: int, max_response_length: int,
+             device: int = 0):
+        """pairs: (output, input) tuples, strictly ascending; responses[n] is
+        the response of pairs[n]."""
+        po, pi = _pair_arrays(pairs)
+        r = _listed_responses(responses, len(po))
+        lst = list(zip(po.tolist(), pi.tolist()))
+        if any(b <= a for a, b in zip(lst, lst[1:])):
+            raise ValueError("the pair list must be strictly ascending in (output, input)")
+        n = r.shape[1]
+        h = lib().fftconv_matrix_sparse_twostage_init(device, inputs, outputs, len(po), po.ctypes.data_as(_u32p),
+                                                      pi.ctypes.data_as(_u32p), _p(r), n, n, max_block_size,
+                                                      max_response_length)
+        return cls(_handle(h), inputs, outputs, lst)
+
+    def update(self, responses):
+        """todo!() in the reference (src/fft_convolver.rs:408-410): raises
+        NotImplementedInReference, the handle is unchanged."""
+        r = _listed_responses(responses, self.pairs)
+        _check(self._fn("update")(self._h, _p(r), r.shape[1], r.shape[1]))
+
+    def reset(self):
+        _check(self._fn("reset")(self._h))
+
+    def process(self, inp) -> np.ndarray:
+        """x[inputs][n <= max_block_size] -> y[outputs][n]."""
+        x = _f32(inp)
+        if x.ndim != 2 or x.shape[0] != self.inputs:
+            raise ValueError(f"input must be [{self.inputs}][n]")
+        n = x.shape[1]
+        y = np.zeros((self.outputs, n), np.float32)
+        _check(self._fn("process")(self._h, _p(x), _p(y), n))
+        return y
+
+    def clone(self):
+        return SparseMatrixTwoStageConvolver(_handle(self._fn("clone")(self._h)), self.inputs, self.outputs,
+                                             self._pair_list)
+
+    @property
+    def pairs(self) -> int:
+        return len(self._pair_list)
+
+    @property
+    def tail_block_size(self) -> int:
+        return int(self._fn("tail_block_size")(self._h))
+
+    def set_fused(self, on: bool):
+        """False: every call takes the composition path (tests, A/B runs)."""
+        _check(self._fn("set_fused")(self._h, 1 if on else 0))
+
+    def path(self, n: int) -> int:
+        """The path the next process() of n samples takes: 0 composition, 1 fused."""
+        return int(self._fn("path")(self._h, n))
+
+
 __all__ = [
     "Fft", "FFTConvolver", "TwoStageFFTConvolver", "CrossfadeConvolver", "MatrixConvolver",
     "MatrixLookaheadConvolver", "SparseMatrixConvolver", "SparseMatrixLookaheadConvolver",
     "MatrixCrossfadeConvolver", "SparseMatrixCrossfadeConvolver", "MatrixTwoStageConvolver",
-    "ConvolutionPanic",
+    "SparseMatrixTwoStageConvolver", "ConvolutionPanic",
     "NotImplementedInReference", "DeviceError", "complex_size", "compute_tail_block_size", "device_count",
     "lib", "LIB_PATH", "SIGNATURES",
 ]

@@ -68,6 +68,7 @@ typedef struct fftconv_matrix_lookahead fftconv_matrix_lookahead; /* the matrix 
 typedef struct fftconv_matrix_sparse_lookahead fftconv_matrix_sparse_lookahead; /* the sparse matrix with far-row windows (below) */
 typedef struct fftconv_matrix_crossfade fftconv_matrix_crossfade; /* inputs x outputs CrossfadeConvolver<FFTConvolver> instances (below) */
 typedef struct fftconv_matrix_twostage fftconv_matrix_twostage;   /* inputs x outputs TwoStageFFTConvolver instances (below) */
+typedef struct fftconv_matrix_sparse_twostage fftconv_matrix_sparse_twostage; /* one TwoStageFFTConvolver per listed pair (below) */
 
 /* ---- library ----------------------------------------------------------- */
 int fftconv_abi_version(void);
@@ -454,9 +455,9 @@ int fftconv_matrix_state(const fftconv_matrix *h, size_t out3[3]);
  * FFTCONV_E_UNSUPPORTED; init returns NULL on error (fftconv_last_error).
  * Crossfaded switching of a sparse matrix is fftconv_matrix_sparse_crossfade
  * (below); far-row windows for a sparse matrix with long responses and small
- * blocks are the fftconv_matrix_sparse_lookahead handle, below.  Out of scope: a sparse
- * two-stage matrix (that takes a dense fftconv_matrix) and changing the pattern
- * after init. */
+ * blocks are the fftconv_matrix_sparse_lookahead handle, below; two-stage
+ * partitioning over a pattern is the fftconv_matrix_sparse_twostage handle
+ * (below).  Out of scope: changing the pattern after init. */
 fftconv_matrix_sparse *fftconv_matrix_sparse_init(int device, size_t inputs, size_t outputs, size_t pairs,
                                                   const uint32_t *pair_out, const uint32_t *pair_in,
                                                   const float *responses, size_t response_len,
@@ -975,6 +976,92 @@ size_t fftconv_matrix_twostage_tail_block_size(const fftconv_matrix_twostage *h)
 int fftconv_matrix_twostage_set_fused(fftconv_matrix_twostage *h, int on);
 /* the path (0 or 1 above) the next process() of `len` samples would take */
 int fftconv_matrix_twostage_path(const fftconv_matrix_twostage *h, size_t len);
+
+/* ---- SparseMatrixTwoStageConvolver: two-stage partitioning over a listed pair set ----
+ * A sparse two-stage matrix has I inputs, O outputs and N >= 1 pairs (o_n, i_n),
+ * strictly ascending in (o, i) as for fftconv_matrix_sparse_init, a head block
+ * max_block_size and max_response_length L.  It behaves as N reference
+ * TwoStageFFTConvolver instances (src/fft_convolver.rs:323-526), one per listed
+ * pair, all created and reset together with the same lengths: instance n
+ * processes input i_n with the same calls, output o is the sum of the
+ * instances listed for it.  An output without pairs is 0.0 for every sample of
+ * every call; an input that no pair reads is accepted and ignored; the pattern
+ * is fixed for the life of the handle.
+ * Stages, T, absent stages, the host's single copy of {tail_input_fill,
+ * precalculated_pos} and the two buffer swaps are the dense two-stage matrix's
+ * (above): tail_output0 / tail_precalculated0 / tail_output /
+ * tail_precalculated summed per output [O][T], tail_input per input [I][T].
+ * Each stage is a SPARSE matrix (fftconv_matrix_sparse_*) over the same pattern:
+ *   head   padded_ir[0 .. min(L, T)],               block max_block_size
+ *   tail0  padded_ir[T .. T + min(L - T, T)],       block max_block_size, only when L > T
+ *   tail   padded_ir[2T .. L],                      block T,              only when L > 2T
+ * Order of summation (part of the contract): each stage's is the sparse
+ * matrix's -- P_o = matrix_parts_rule(k_o, active) per output, rows flattened
+ * pair-major in list order, the row-0 terms in ascending e -- and the sums
+ * ((y / N + ovl) + tail_precalculated0) + tail_precalculated are in the dense
+ * two-stage's order.  So
+ *  1. output o is bit-identical to the single output of a dense
+ *     fftconv_matrix_twostage with k_o inputs that holds h[pair e] and is fed
+ *     x[i_e] in list order;
+ *  2. an output's bits depend on nothing outside its own pair list: a pattern
+ *     split by outputs over several handles computes identical rows;
+ *  3. both paths below compute the same bits.
+ * Mirrored from the reference, as the dense handle: len > max_block_size is
+ * FFTCONV_E_INVALID (:414); a head block that does not divide T is
+ * FFTCONV_E_INVALID at the call where the reference panics (:459-460); update
+ * is FFTCONV_E_UNIMPLEMENTED with the handle unchanged (:408-410).  Pattern
+ * errors as fftconv_matrix_sparse_init (FFTCONV_E_INVALID); response_len > L is
+ * FFTCONV_E_INVALID; a block outside 32..8192 or T > 8192 is
+ * FFTCONV_E_UNSUPPORTED before anything is allocated.  A failed launch between
+ * the stages makes every later call fail (FFTCONV_E_DEVICE).  init returns NULL
+ * on error (fftconv_last_error).  Responses are in pair-list order, row n at
+ * responses + n * response_stride; stride 0 = one response for every pair.
+ * Streams and signatures as fftconv_matrix_twostage_*; the call that ends a
+ * period carries the tail's block-T convolution inline.
+ * Paths (fftconv_matrix_sparse_twostage_path) -- both compute the same bits:
+ *   0  composition: the three sparse stages and the dense handle's sub-chunk
+ *      kernel.
+ *   1  fused: head, the sub-chunk and tail0 in the sparse matrix's two launches
+ *      -- one forward transform per input for both delay lines, every delay-
+ *      line row and pattern entry loaded once for both responses.  Taken under
+ *      the dense handle's conditions (an aligned call, tail0 exists, equal
+ *      segment counts) and equal MAC plans of head and tail0.
+ * Out of scope: update / update_pairs, changing the pattern after init, T >
+ * 8192, a crossfade over two-stage matrices. */
+fftconv_matrix_sparse_twostage *fftconv_matrix_sparse_twostage_init(int device, size_t inputs, size_t outputs,
+                                                                    size_t pairs, const uint32_t *pair_out,
+                                                                    const uint32_t *pair_in, const float *responses,
+                                                                    size_t response_len, size_t response_stride,
+                                                                    size_t max_block_size, size_t max_response_length);
+/* :408-410: FFTCONV_E_UNIMPLEMENTED */
+int fftconv_matrix_sparse_twostage_update(fftconv_matrix_sparse_twostage *h, const float *responses,
+                                          size_t response_len, size_t response_stride);
+int fftconv_matrix_sparse_twostage_reset(fftconv_matrix_sparse_twostage *h); /* :497-511 */
+/* input [inputs][len], output [outputs][len], host memory. */
+int fftconv_matrix_sparse_twostage_process(fftconv_matrix_sparse_twostage *h, const float *input, float *output,
+                                           size_t len);
+/* device memory, stream-ordered: input i at d_input + i * in_stride, output o
+ * at d_output + o * out_stride (strides in floats). */
+int fftconv_matrix_sparse_twostage_process_device(fftconv_matrix_sparse_twostage *h, const float *d_input,
+                                                  size_t in_stride, float *d_output, size_t out_stride, size_t len,
+                                                  void *hip_stream);
+/* `steps` consecutive process_device calls; the same bits as the separate calls. */
+int fftconv_matrix_sparse_twostage_process_device_steps(fftconv_matrix_sparse_twostage *h, const float *d_input,
+                                                        size_t in_stride, size_t in_step, float *d_output,
+                                                        size_t out_stride, size_t out_step, size_t len, size_t steps,
+                                                        void *hip_stream);
+fftconv_matrix_sparse_twostage *fftconv_matrix_sparse_twostage_clone(const fftconv_matrix_sparse_twostage *h);
+void fftconv_matrix_sparse_twostage_destroy(fftconv_matrix_sparse_twostage *h);
+int fftconv_matrix_sparse_twostage_synchronize(fftconv_matrix_sparse_twostage *h);
+size_t fftconv_matrix_sparse_twostage_inputs(const fftconv_matrix_sparse_twostage *h);
+size_t fftconv_matrix_sparse_twostage_outputs(const fftconv_matrix_sparse_twostage *h);
+size_t fftconv_matrix_sparse_twostage_pairs(const fftconv_matrix_sparse_twostage *h);
+size_t fftconv_matrix_sparse_twostage_tail_block_size(const fftconv_matrix_sparse_twostage *h);
+/* tests and A/B runs: on = 0 makes every call of this handle take the
+ * composition path (default 1); a clone inherits the setting. */
+int fftconv_matrix_sparse_twostage_set_fused(fftconv_matrix_sparse_twostage *h, int on);
+/* the path (0 or 1 above) the next process() of `len` samples would take */
+int fftconv_matrix_sparse_twostage_path(const fftconv_matrix_sparse_twostage *h, size_t len);
 
 #ifdef __cplusplus
 }
