@@ -30,7 +30,8 @@ namespace fftconv {
 namespace {
 
 // Launch A: blocks [0, I) are the R2C workgroups, blocks I + o * P + p the MAC
-// workgroups (launched only for a chunk that starts a block).
+// workgroups (launched only for a chunk that starts a block): the row walk over
+// the dense rows 1 <= s < active (sites 50, 51).
 template <int LOG2B, int NT, bool NTL>
 __global__ __launch_bounds__(NT) void matrix_a_kernel(MatrixArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -38,8 +39,7 @@ __global__ __launch_bounds__(NT) void matrix_a_kernel(MatrixArgs a) {
     if (b < a.I) {
         matrix_r2c<LOG2B, NT>(a, b, smem);
     } else {
-        const int m = b - a.I;
-        matrix_mac<LOG2B, NT, NTL>(a, m / a.P, m % a.P, smem);
+        matrix_row_walk<LOG2B, NT, NTL, 50>(dense_rows(a, b - a.I, 51), MacStreams{a}, a.act - 1, smem);
     }
 }
 
@@ -53,7 +53,6 @@ __global__ __launch_bounds__(NT) void matrix_b_kernel(MatrixArgs a) {
     using Gm = MGeo<LOG2B, NT>;
     constexpr int B = Gm::B, F = Gm::F, SPT = Gm::SPT;
     constexpr int UB = SPT == 1 ? 16 : (SPT == 2 ? 8 : 4);  // terms in flight per slot
-    constexpr float invN = 1.0f / (float)(2 * B);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float2 *bufA = reinterpret_cast<float2 *>(smem);
     float2 *bufB = bufA + B;
@@ -102,17 +101,11 @@ __global__ __launch_bounds__(NT) void matrix_b_kernel(MatrixArgs a) {
             reinterpret_cast<float4 *>(bufA)[f] = v;
         }
     }
-    __syncthreads();
-    for (int m = tid; m < B; m += NT) bufB[m] = real_pre<LOG2B, NT>(bufA, m, a.tw);
-    __syncthreads();
-    const float *y = reinterpret_cast<const float *>(lds_cfft<LOG2B, NT, true>(bufB, bufA, a.tw));
+    const float *y = finish_c2r<LOG2B, NT>(bufA, bufB, a.tw);
     float *outc = a.out + (long long)o * a.out_stride;
     float *ovc = a.ovl + (size_t)o * B;
-    for (int j = tid; j < k; j += NT) outc[j] = y[fill + j] * invN + ovc[fill + j];
-    if (complete) {
-        __syncthreads();  // (every overlap read above is done)
-        for (int j = tid; j < B; j += NT) ovc[j] = y[B + j] * invN;
-    }
+    overlap_add<LOG2B, NT>(y, ovc, fill, k, [&](int j, float v) { outc[j] = v; });
+    if (complete) overlap_save<LOG2B, NT>(y, ovc);
 }
 
 template <int LOG2B>
@@ -138,9 +131,7 @@ int matrix_mac_parts(int inputs, int log2b, int seg_count, int active) {
 }
 
 hipError_t launch_matrix_chunk(int log2b, const MatrixArgs &a, hipStream_t s) {
-    if (a.I <= 0 || a.O <= 0 || a.k <= 0 || a.act <= 0 || a.P <= 0 || a.fill < 0 || a.fill + a.k > (1 << log2b) ||
-        a.cur < 0 || a.cur >= a.S || a.act > a.S)
-        return hipErrorInvalidValue;
+    if (!matrix_chunk_in_range(log2b, a.I, a.O, a.S, a.cur, a.act, a.fill, a.k) || a.P <= 0) return hipErrorInvalidValue;
     if ((long long)a.I + (long long)a.O * a.P > (long long)INT32_MAX) return hipErrorInvalidValue;
     return dispatch_log2<5, kMaxLog2Fused>(log2b, hipErrorInvalidValue,
                                            [&](auto L) { return launch_matrix_t<L()>(a, s); });

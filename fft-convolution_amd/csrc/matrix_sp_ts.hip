@@ -41,57 +41,30 @@
 namespace fftconv {
 namespace {
 
-// matrix_ts.hip's ts_r2c: matrix_r2c of a whole block (fill 0, k = B: the input
-// buffers stay zero) for both delay lines, and the block's copy into tail_input
-template <int LOG2B, int NT>
-__device__ __forceinline__ void spts_r2c(const MatrixSpTsArgs &a, int i, unsigned char *smem) {
-    constexpr int B = 1 << LOG2B;
-    float2 *bufA = reinterpret_cast<float2 *>(smem);
-    float2 *bufB = bufA + B;
-    const int tid = threadIdx.x;
-    const float *inc = a.in + (long long)i * a.in_stride;
-    float *tic = a.tin + (long long)i * a.T;
-    for (int m = tid; m < B; m += NT) {
-        float2 z = make_float2(0.f, 0.f);
-        if (2 * m < B) {
-            z.x = inc[2 * m];
-            z.y = inc[2 * m + 1];
-            tic[2 * m] = z.x;
-            tic[2 * m + 1] = z.y;
-        }
-        bufA[m] = z;
-    }
-    __syncthreads();
-    const float2 *Z = lds_cfft<LOG2B, NT, false>(bufA, bufB, a.tw);
-    const size_t at = ((size_t)i * a.S + a.cur) * B;
-    float2 *row0 = a.X[0] + at, *row1 = a.X[1] + at;
-    for (int m = tid; m < B; m += NT) row0[m] = row1[m] = real_post<LOG2B, NT>(Z, m, a.tw);
-}
-
 template <int LOG2B, int NT, bool NTL>
 __global__ __launch_bounds__(NT) void matrix_sp_ts_a_kernel(MatrixSpTsArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int b = blockIdx.x;
     if (b < a.I) {
-        spts_r2c<LOG2B, NT>(a, b, smem);
+        matrix_r2c_block<LOG2B, NT>(a, b, smem);
         return;
     }
-    // (the walk is matrix_sp.hpp's; its DBG_CHECK sites are 77, 78 and 79)
-    matrix_sp_mac_streams<LOG2B, NT, NTL, 2, 77>(a, b - a.I, 0, smem);
+    // (the row walk over the pair list, two H streams; its DBG_CHECK sites are 77, 78 and 79)
+    matrix_row_walk<LOG2B, NT, NTL, 77>(listed_rows(a.wg, a.col, b - a.I, a.PT, a.N, 78),
+                                        MacStreamsPair<MatrixSpTsArgs>{a}, a.act - 1, smem);
 }
 
 // Launch B, workgroup = (output o, matrix c): matrix_sp_b_kernel's finish of a
 // whole block (fill 0, k = B), c = 0 for the head, c = 1 for tail0, side by
-// side as matrix_ts_b_kernel (the finish is a latency chain).  An output
-// without pairs has one all-zero part and no terms: it writes zeros (plus the
-// precalculated sums, which are zero for it too) and keeps a zero overlap in
-// both stages.
+// side as matrix_ts_b_kernel (the finish is a latency chain), with its epilogue
+// (ts_epilogue).  An output without pairs has one all-zero part and no terms: it
+// writes zeros (plus the precalculated sums, which are zero for it too) and
+// keeps a zero overlap in both stages.
 template <int LOG2B, int NT>
 __global__ __launch_bounds__(NT) void matrix_sp_ts_b_kernel(MatrixSpTsArgs a) {
     using Gm = MGeo<LOG2B, NT>;
     constexpr int B = Gm::B, F = Gm::F, SPT = Gm::SPT;
     constexpr int UB = SPT == 1 ? 16 : (SPT == 2 ? 8 : 4);  // terms in flight per slot
-    constexpr float invN = 1.0f / (float)(2 * B);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float2 *bufA = reinterpret_cast<float2 *>(smem);
     float2 *bufB = bufA + B;
@@ -150,27 +123,8 @@ __global__ __launch_bounds__(NT) void matrix_sp_ts_b_kernel(MatrixSpTsArgs a) {
             reinterpret_cast<float4 *>(bufA)[f] = v;
         }
     }
-    __syncthreads();
-    for (int m = tid; m < B; m += NT) bufB[m] = real_pre<LOG2B, NT>(bufA, m, a.tw);
-    __syncthreads();
-    const float *y = reinterpret_cast<const float *>(lds_cfft<LOG2B, NT, true>(bufB, bufA, a.tw));
-    float *ovc = a.ovl[c] + (size_t)o * B;
-    if (c == 0) {
-        float *outc = a.out + (long long)o * a.out_stride;
-        const float *p0 = a.p0 + (long long)o * a.T;
-        const float *p1 = a.p1 ? a.p1 + (long long)o * a.T : nullptr;
-        for (int j = tid; j < B; j += NT) {
-            float v = y[j] * invN + ovc[j];  // the head's sample (:417)
-            v += p0[j];                      // :439-445
-            if (p1) v += p1[j];              // :448-454
-            outc[j] = v;
-        }
-    } else {
-        float *t0c = a.tout0 + (long long)o * a.T;
-        for (int j = tid; j < B; j += NT) t0c[j] = y[j] * invN + ovc[j];
-    }
-    __syncthreads();  // (every overlap read above is done)
-    for (int j = tid; j < B; j += NT) ovc[j] = y[B + j] * invN;
+    const float *y = finish_c2r<LOG2B, NT>(bufA, bufB, a.tw);
+    ts_epilogue<LOG2B, NT>(a, o, c, y);
 }
 
 template <int LOG2B>
@@ -187,8 +141,8 @@ hipError_t launch_matrix_sp_ts_t(const MatrixSpTsArgs &a, hipStream_t s) {
 }  // namespace
 
 hipError_t launch_matrix_sp_ts_block(int log2b, const MatrixSpTsArgs &a, hipStream_t s) {
-    if (a.I <= 0 || a.O <= 0 || a.N <= 0 || a.act <= 0 || a.PT < a.O || a.cur < 0 || a.cur >= a.S || a.act > a.S ||
-        !a.rowptr || !a.col || !a.plan || !a.wg || a.T < (1LL << log2b) || !a.tin || !a.tout0 || !a.p0)
+    if (!matrix_chunk_in_range(log2b, a.I, a.O, a.S, a.cur, a.act, 0, 1 << log2b) || a.N <= 0 || a.PT < a.O || !a.rowptr ||
+        !a.col || !a.plan || !a.wg || a.T < (1LL << log2b) || !a.tin || !a.tout0 || !a.p0)
         return hipErrorInvalidValue;
     for (int c = 0; c < 2; ++c)
         if (!a.H[c] || !a.X[c] || !a.ovl[c] || !a.part[c]) return hipErrorInvalidValue;

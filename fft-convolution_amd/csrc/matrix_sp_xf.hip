@@ -6,7 +6,7 @@
 //   launch A  [0, I)   one R2C per input, the row written to X_A and X_B, both
 //                      input buffers maintained
 //             I + m    (a chunk that starts a block) MAC workgroup m < PT =
-//                      (output o, part p) from wg[m]: matrix_sp_mac's walk on
+//                      (output o, part p) from wg[m]: the listed row walk on
 //                      the live convolver's H, or -- both live -- one pass with
 //                      every X row and `col` entry loaded once for H_A and H_B
 //             last     (first chunk of a call inside a fade) one lane walks
@@ -36,43 +36,6 @@
 namespace fftconv {
 namespace {
 
-// matrix_r2c for both convolvers (as matrix_xf.hip's): ib_A == ib_B and the row
-// is the same, so one transform, every store twice.
-template <int LOG2B, int NT>
-__device__ __forceinline__ void spxf_r2c(const MatrixSpXfArgs &a, int i, unsigned char *smem) {
-    constexpr int B = 1 << LOG2B;
-    float2 *bufA = reinterpret_cast<float2 *>(smem);
-    float2 *bufB = bufA + B;
-    const int tid = threadIdx.x;
-    const int fill = a.fill, k = a.k;
-    const float *inc = a.in + (long long)i * a.in_stride;
-    float *ib0 = a.ib[0] + (size_t)i * B, *ib1 = a.ib[1] + (size_t)i * B;
-    auto sample = [&](int j) -> float {
-        if (j < fill) return ib0[j];
-        if (j < fill + k) return inc[j - fill];
-        return 0.f;
-    };
-    for (int m = tid; m < B; m += NT) {
-        float2 z = make_float2(0.f, 0.f);
-        if (2 * m < B) {
-            z.x = sample(2 * m);
-            z.y = sample(2 * m + 1);
-        }
-        bufA[m] = z;
-    }
-    __syncthreads();  // (every read of ib[i] is done)
-    if (fill + k == B) {
-        if (fill > 0)
-            for (int j = tid; j < B; j += NT) ib0[j] = ib1[j] = 0.f;
-    } else {
-        for (int j = tid; j < k; j += NT) ib0[fill + j] = ib1[fill + j] = inc[j];
-    }
-    const float2 *Z = lds_cfft<LOG2B, NT, false>(bufA, bufB, a.tw);
-    const size_t at = ((size_t)i * a.S + a.cur) * B;
-    float2 *row0 = a.X[0] + at, *row1 = a.X[1] + at;
-    for (int m = tid; m < B; m += NT) row0[m] = row1[m] = real_post<LOG2B, NT>(Z, m, a.tw);
-}
-
 // PAIR = both convolvers live.  Two kernels, not one branch: the one-stream MAC
 // of the idle state then keeps the plain sparse MAC's register budget (one
 // kernel for both took SP1's idle block from 21.1 to 23.7 us).
@@ -85,15 +48,15 @@ __global__ __launch_bounds__(NT) void matrix_sp_xf_a_kernel(MatrixSpXfArgs a) {
         return;
     }
     if (b < a.I) {
-        spxf_r2c<LOG2B, NT>(a, b, smem);
+        matrix_r2c_pair<LOG2B, NT>(a, b, smem);
         return;
     }
-    const int m = b - a.I;
-    // (the walk is matrix_sp.hpp's; its DBG_CHECK sites are 63, 64 and 65)
+    // (the row walk over the pair list; its DBG_CHECK sites are 63, 64 and 65)
+    const ListedRows rw = listed_rows(a.wg, a.col, b - a.I, a.PT, a.N, 64);
     if constexpr (PAIR)
-        matrix_sp_mac_streams<LOG2B, NT, NTL, 2, 63>(a, m, 0, smem);
+        matrix_row_walk<LOG2B, NT, NTL, 63>(rw, MacStreamsPair<MatrixSpXfArgs>{a}, a.act - 1, smem);
     else
-        matrix_sp_mac_streams<LOG2B, NT, NTL, 1, 63>(a, m, a.live == 1 ? 0 : 1, smem);
+        matrix_row_walk<LOG2B, NT, NTL, 63>(rw, MacStreamsOf<MatrixSpXfArgs>{a, a.live == 1 ? 0 : 1}, a.act - 1, smem);
 }
 
 // Launch B, workgroup = output o: matrix_sp_b_kernel's finish for each live
@@ -216,9 +179,8 @@ hipError_t launch_matrix_sp_xf_t(const MatrixSpXfArgs &a, hipStream_t s) {
 }  // namespace
 
 hipError_t launch_matrix_sp_xf_chunk(int log2b, const MatrixSpXfArgs &a, hipStream_t s) {
-    if (a.I <= 0 || a.O <= 0 || a.N <= 0 || a.k <= 0 || a.act <= 0 || a.PT < a.O || a.fill < 0 ||
-        a.fill + a.k > (1 << log2b) || a.cur < 0 || a.cur >= a.S || a.act > a.S || !a.rowptr || !a.col || !a.plan ||
-        !a.wg || a.live < 1 || a.live > 3 || a.off < 0 || a.mix.n < 0)
+    if (!matrix_chunk_in_range(log2b, a.I, a.O, a.S, a.cur, a.act, a.fill, a.k) || a.N <= 0 || a.PT < a.O || !a.rowptr ||
+        !a.col || !a.plan || !a.wg || a.live < 1 || a.live > 3 || a.off < 0 || a.mix.n < 0)
         return hipErrorInvalidValue;
     if (a.mix.approaching && !a.mix.vtab) return hipErrorInvalidValue;
     if ((long long)a.I + (long long)a.PT + 1 > (long long)INT32_MAX) return hipErrorInvalidValue;

@@ -8,8 +8,9 @@
 //                          (src/fft_convolver.rs:459-461) from the registers
 //                          that feed the transform
 //             I + o*P + p  the MAC of (output o, part p) for both responses in
-//                          one pass over the rows (matrix_mac_pair): every X
-//                          row loaded once, from the head's delay line
+//                          one pass over the rows (the row walk over two H
+//                          streams): every X row loaded once, from the head's
+//                          delay line
 //   launch B  (o, 0)       the head's finish (sum of parts, + X[cur] (.) H[0],
 //                          C2R, overlap-add) with the sub-chunk sums of
 //                          :438-454 in its epilogue:
@@ -38,48 +39,21 @@
 namespace fftconv {
 namespace {
 
-// matrix_r2c of a whole block (fill 0, k = B: the input buffers stay zero) for
-// both delay lines, and the block's copy into tail_input
-template <int LOG2B, int NT>
-__device__ __forceinline__ void ts_r2c(const MatrixTsArgs &a, int i, unsigned char *smem) {
-    constexpr int B = 1 << LOG2B;
-    float2 *bufA = reinterpret_cast<float2 *>(smem);
-    float2 *bufB = bufA + B;
-    const int tid = threadIdx.x;
-    const float *inc = a.in + (long long)i * a.in_stride;
-    float *tic = a.tin + (long long)i * a.T;
-    for (int m = tid; m < B; m += NT) {
-        float2 z = make_float2(0.f, 0.f);
-        if (2 * m < B) {
-            z.x = inc[2 * m];
-            z.y = inc[2 * m + 1];
-            tic[2 * m] = z.x;
-            tic[2 * m + 1] = z.y;
-        }
-        bufA[m] = z;
-    }
-    __syncthreads();
-    const float2 *Z = lds_cfft<LOG2B, NT, false>(bufA, bufB, a.tw);
-    const size_t at = ((size_t)i * a.S + a.cur) * B;
-    float2 *row0 = a.X[0] + at, *row1 = a.X[1] + at;
-    for (int m = tid; m < B; m += NT) row0[m] = row1[m] = real_post<LOG2B, NT>(Z, m, a.tw);
-}
-
+// (DBG_CHECK sites 52, 53: the two-stream walk's)
 template <int LOG2B, int NT, bool NTL>
 __global__ __launch_bounds__(NT) void matrix_ts_a_kernel(MatrixTsArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int b = blockIdx.x;
     if (b < a.I) {
-        ts_r2c<LOG2B, NT>(a, b, smem);
+        matrix_r2c_block<LOG2B, NT>(a, b, smem);
         return;
     }
-    const int m = b - a.I;
-    matrix_mac_pair<LOG2B, NT, NTL>(a, m / a.P, m % a.P, smem);
+    matrix_row_walk<LOG2B, NT, NTL, 52>(dense_rows(a, b - a.I, 53), MacStreamsPair<MatrixTsArgs>{a}, a.act - 1, smem);
 }
 
 // Launch B, workgroup = (output o, matrix c): matrix_b_kernel's finish of a
-// whole block (fill 0, k = B), c = 0 for the head, c = 1 for tail0.  The two
-// finishes touch disjoint buffers, so they run side by side: the finish is a
+// whole block (fill 0, k = B), c = 0 for the head, c = 1 for tail0, with the
+// two-stage epilogue (ts_epilogue, matrix.hpp).  The two finishes touch disjoint buffers, so they run side by side: the finish is a
 // latency chain (I + P dependent loads, two transforms), and one workgroup
 // running both in turn took 12.6 us (32 x 32, B 64) / 20.2 us (64 x 2, B 256)
 // per block against 8.7 / 13.4 us for the plain finish (profiles/matrix_ts).
@@ -88,7 +62,6 @@ __global__ __launch_bounds__(NT) void matrix_ts_b_kernel(MatrixTsArgs a) {
     using Gm = MGeo<LOG2B, NT>;
     constexpr int B = Gm::B, F = Gm::F, SPT = Gm::SPT;
     constexpr int UB = SPT == 1 ? 16 : (SPT == 2 ? 8 : 4);  // terms in flight per slot
-    constexpr float invN = 1.0f / (float)(2 * B);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float2 *bufA = reinterpret_cast<float2 *>(smem);
     float2 *bufB = bufA + B;
@@ -129,27 +102,8 @@ __global__ __launch_bounds__(NT) void matrix_ts_b_kernel(MatrixTsArgs a) {
             reinterpret_cast<float4 *>(bufA)[f] = v;
         }
     }
-    __syncthreads();
-    for (int m = tid; m < B; m += NT) bufB[m] = real_pre<LOG2B, NT>(bufA, m, a.tw);
-    __syncthreads();
-    const float *y = reinterpret_cast<const float *>(lds_cfft<LOG2B, NT, true>(bufB, bufA, a.tw));
-    float *ovc = a.ovl[c] + (size_t)o * B;
-    if (c == 0) {
-        float *outc = a.out + (long long)o * a.out_stride;
-        const float *p0 = a.p0 + (long long)o * a.T;
-        const float *p1 = a.p1 ? a.p1 + (long long)o * a.T : nullptr;
-        for (int j = tid; j < B; j += NT) {
-            float v = y[j] * invN + ovc[j];  // the head's sample (:417)
-            v += p0[j];                      // :439-445
-            if (p1) v += p1[j];              // :448-454
-            outc[j] = v;
-        }
-    } else {
-        float *t0c = a.tout0 + (long long)o * a.T;
-        for (int j = tid; j < B; j += NT) t0c[j] = y[j] * invN + ovc[j];
-    }
-    __syncthreads();  // (every overlap read above is done)
-    for (int j = tid; j < B; j += NT) ovc[j] = y[B + j] * invN;
+    const float *y = finish_c2r<LOG2B, NT>(bufA, bufB, a.tw);
+    ts_epilogue<LOG2B, NT>(a, o, c, y);
 }
 
 // the sub-chunk of the composition path: blocks [0, O) the outputs' sums,
@@ -189,8 +143,8 @@ hipError_t launch_matrix_ts_t(const MatrixTsArgs &a, hipStream_t s) {
 }  // namespace
 
 hipError_t launch_matrix_ts_block(int log2b, const MatrixTsArgs &a, hipStream_t s) {
-    if (a.I <= 0 || a.O <= 0 || a.act <= 0 || a.P <= 0 || a.cur < 0 || a.cur >= a.S || a.act > a.S ||
-        a.T < (1LL << log2b) || !a.tin || !a.tout0 || !a.p0)
+    if (!matrix_chunk_in_range(log2b, a.I, a.O, a.S, a.cur, a.act, 0, 1 << log2b) || a.P <= 0 || a.T < (1LL << log2b) ||
+        !a.tin || !a.tout0 || !a.p0)
         return hipErrorInvalidValue;
     if ((long long)a.I + (long long)a.O * a.P > (long long)INT32_MAX) return hipErrorInvalidValue;
     return dispatch_log2<5, kMaxLog2Fused>(log2b, hipErrorInvalidValue,

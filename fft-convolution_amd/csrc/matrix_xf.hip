@@ -7,9 +7,9 @@
 //             last         (first chunk of a call inside a fade) one lane walks
 //                          mix_value into the call's device table
 //             I + o*P + p  the MAC of (output o, part p), for a chunk that
-//                          starts a block: matrix_mac on the live convolver's H,
-//                          or -- both live -- one pass over the rows with every
-//                          X row loaded once for H_A and H_B
+//                          starts a block: the row walk on the live convolver's
+//                          H, or -- both live -- one pass over the rows with
+//                          every X row loaded once for H_A and H_B
 //   launch B  o            per live convolver the finish of matrix_b_kernel
 //                          (sum of parts or kept pre, + X[cur] (.) H[0], C2R,
 //                          overlap-add, overlap / pre kept), then the mix
@@ -47,7 +47,7 @@ __device__ __forceinline__ MatrixArgs xf_view(const MatrixXfArgs &a, int c) {
     return m;
 }
 
-// the launches' dynamic LDS (launch A's MAC is matrix_mac_pair)
+// the launches' dynamic LDS (launch A's MAC may walk two H streams)
 template <int LOG2B, int NT>
 struct XGeo {
     using Gm = MGeo<LOG2B, NT>;
@@ -55,43 +55,7 @@ struct XGeo {
     static constexpr size_t lds_b = Gm::fft_bytes;
 };
 
-// matrix_r2c for both convolvers: ib_A == ib_B and the row is the same, so one
-// transform, every store twice.
-template <int LOG2B, int NT>
-__device__ __forceinline__ void xf_r2c(const MatrixXfArgs &a, int i, unsigned char *smem) {
-    constexpr int B = 1 << LOG2B;
-    float2 *bufA = reinterpret_cast<float2 *>(smem);
-    float2 *bufB = bufA + B;
-    const int tid = threadIdx.x;
-    const int fill = a.fill, k = a.k;
-    const float *inc = a.in + (long long)i * a.in_stride;
-    float *ib0 = a.ib[0] + (size_t)i * B, *ib1 = a.ib[1] + (size_t)i * B;
-    auto sample = [&](int j) -> float {
-        if (j < fill) return ib0[j];
-        if (j < fill + k) return inc[j - fill];
-        return 0.f;
-    };
-    for (int m = tid; m < B; m += NT) {
-        float2 z = make_float2(0.f, 0.f);
-        if (2 * m < B) {
-            z.x = sample(2 * m);
-            z.y = sample(2 * m + 1);
-        }
-        bufA[m] = z;
-    }
-    __syncthreads();  // (every read of ib[i] is done)
-    if (fill + k == B) {
-        if (fill > 0)
-            for (int j = tid; j < B; j += NT) ib0[j] = ib1[j] = 0.f;
-    } else {
-        for (int j = tid; j < k; j += NT) ib0[fill + j] = ib1[fill + j] = inc[j];
-    }
-    const float2 *Z = lds_cfft<LOG2B, NT, false>(bufA, bufB, a.tw);
-    const size_t at = ((size_t)i * a.S + a.cur) * B;
-    float2 *row0 = a.X[0] + at, *row1 = a.X[1] + at;
-    for (int m = tid; m < B; m += NT) row0[m] = row1[m] = real_post<LOG2B, NT>(Z, m, a.tw);
-}
-
+// (DBG_CHECK sites: 50, 51 one convolver live; 52, 53 both)
 template <int LOG2B, int NT, bool NTL>
 __global__ __launch_bounds__(NT) void matrix_xf_a_kernel(MatrixXfArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -101,14 +65,16 @@ __global__ __launch_bounds__(NT) void matrix_xf_a_kernel(MatrixXfArgs a) {
         return;
     }
     if (b < a.I) {
-        xf_r2c<LOG2B, NT>(a, b, smem);
+        matrix_r2c_pair<LOG2B, NT>(a, b, smem);
         return;
     }
     const int m = b - a.I;
     if (a.live == 3)
-        matrix_mac_pair<LOG2B, NT, NTL>(a, m / a.P, m % a.P, smem);
-    else
-        matrix_mac<LOG2B, NT, NTL>(xf_view(a, a.live == 1 ? 0 : 1), m / a.P, m % a.P, smem);
+        matrix_row_walk<LOG2B, NT, NTL, 52>(dense_rows(a, m, 53), MacStreamsPair<MatrixXfArgs>{a}, a.act - 1, smem);
+    else {
+        const MatrixArgs v = xf_view(a, a.live == 1 ? 0 : 1);
+        matrix_row_walk<LOG2B, NT, NTL, 50>(dense_rows(v, m, 51), MacStreams{v}, v.act - 1, smem);
+    }
 }
 
 // Launch B, workgroup = output o: matrix_b_kernel's finish for each live
@@ -209,8 +175,8 @@ hipError_t launch_matrix_xf_t(const MatrixXfArgs &a, hipStream_t s) {
 }  // namespace
 
 hipError_t launch_matrix_xf_chunk(int log2b, const MatrixXfArgs &a, hipStream_t s) {
-    if (a.I <= 0 || a.O <= 0 || a.k <= 0 || a.act <= 0 || a.P <= 0 || a.fill < 0 || a.fill + a.k > (1 << log2b) ||
-        a.cur < 0 || a.cur >= a.S || a.act > a.S || a.live < 1 || a.live > 3 || a.off < 0 || a.mix.n < 0)
+    if (!matrix_chunk_in_range(log2b, a.I, a.O, a.S, a.cur, a.act, a.fill, a.k) || a.P <= 0 || a.live < 1 || a.live > 3 ||
+        a.off < 0 || a.mix.n < 0)
         return hipErrorInvalidValue;
     if (a.mix.approaching && !a.mix.vtab) return hipErrorInvalidValue;
     if ((long long)a.I + (long long)a.O * a.P + 1 > (long long)INT32_MAX) return hipErrorInvalidValue;

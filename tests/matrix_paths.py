@@ -1,8 +1,8 @@
 """CPU model of which MatrixConvolver kernel paths a shape runs
 (fft-convolution_amd/csrc/matrix.hip): geo() mirrors MGeo, matrix_nt and
 matrix_b_kernel's UB, parts() the matrix_mac_parts rule, walk() replays
-matrix_mac's row walk for every (part, group).  The constants are duplicated on
-purpose: tests/test_matrix_ref.py asserts, for every shape of SHAPES, the
+matrix_row_walk (matrix.hpp) over the dense rows for every (part, group).  The
+constants are duplicated on purpose: tests/test_matrix_ref.py asserts, for every shape of SHAPES, the
 property the shape is there for, so a change of U / G / UB / the P rule fails
 with "shape X no longer reaches path Y"; tests/test_gpu_matrix.py asserts that
 the library's mac_parts equals the model's P."""
@@ -23,7 +23,7 @@ def geo(B):
     F = B // 2                                          # 16-byte slots per row
     G = 1 if F >= NT else NT // F                       # row groups of a MAC workgroup
     SPT = F // NT if F >= NT else 1                     # slots per thread
-    U = {1: 8, 2: 4, 4: 2}.get(SPT, 1)                  # rows in flight (matrix_mac)
+    U = {1: 8, 2: 4, 4: 2}.get(SPT, 1)                  # rows in flight (matrix_row_walk)
     UB = {1: 16, 2: 8}.get(SPT, 4)                      # terms in flight (matrix_b_kernel)
     return Geo(NT, F, G, SPT, U, UB)
 
@@ -35,7 +35,7 @@ def parts(I, act):
 
 
 def walk(B, I, act):
-    """matrix_mac over every (part, group) of one block with `act` active
+    """matrix_row_walk over every (part, group) of one block with `act` active
     segments: unrolled = iterations of the U-rows-in-flight loop, tail = rows of
     the tail loop, groups_both = groups that run both loops, max_cross = the most
     inputs one advance() steps over, cross_in_unrolled = an unrolled iteration

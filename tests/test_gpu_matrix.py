@@ -260,7 +260,7 @@ def test_errors(amd):
 
 
 # ---------------------------------------------------------------------------
-# Path coverage (matrix_paths): shapes at which matrix_mac's unrolled loop, its
+# Path coverage (matrix_paths): shapes at which matrix_row_walk's unrolled loop, its
 # hand-over to the tail loop, several parts at every block size, the P cap and
 # matrix_b_kernel's chunked sums run; tests/test_matrix_ref.py proves on the
 # CPU that each shape reaches the path it is listed for.

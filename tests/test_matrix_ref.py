@@ -34,7 +34,7 @@ def test_summed_oracle_matches_direct(oracle_mod, name, I, O, B, L, lengths):
 @pytest.mark.parametrize("s", SHAPES, ids=shape_id)
 def test_shape_reaches_its_paths(s):
     """Each shape of the GPU path tests runs the kernel paths it is listed
-    for, by the model of matrix_mac / matrix_b_kernel; the walk visits every
+    for, by the model of matrix_row_walk / matrix_b_kernel; the walk visits every
     row exactly once."""
     g, w = geo(s.B), walk(s.B, s.I, s.S)
     print(f"{shape_id(s)}: {g} {w}")
@@ -55,7 +55,7 @@ def test_model_reproduces_the_old_shapes():
 
 
 def test_walk_partitions_the_rows():
-    """matrix_mac's (part, group) walk visits every row once for every block
+    """matrix_row_walk's (part, group) walk visits every row once for every block
     size, 1..13 inputs and 0..70 active segments (P = 1..15), and above the
     P cap."""
     for log2b in range(5, 14):

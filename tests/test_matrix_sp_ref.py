@@ -69,7 +69,7 @@ def test_patterns_are_valid():
 
 @pytest.mark.parametrize("s", BITWISE, ids=lambda s: s.name)
 def test_outputs_reach_their_paths(s):
-    """Each output of a bitwise shape runs, by the model of matrix_mac with
+    """Each output of a bitwise shape runs, by the model of matrix_row_walk with
     inputs := k_o, the loops it is listed for; the walk visits every row of the
     output's list exactly once."""
     assert len(s.why) == len(s.cols)
