@@ -66,6 +66,29 @@ int ilog2(size_t v) {
 }
 size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }  // == (a as f64 / b as f64).ceil()
 
+// (tests: FFTCONV_POISON_ALLOC=1 fills every new buffer with 0xff bytes (NaN as
+// float, -1 as an index), so a read of memory the path never wrote shows in the
+// output instead of reading whatever the allocator recycled.  Every allocation
+// of this file asks here: DevPtr, the shared twiddle / long-block / Bluestein
+// tables, the public Fft's stream-ordered scratch and the pinned host stages.
+// Read once per process; the first poisoned allocation says so on stderr, which
+// is how tests/test_gpu_poison.py knows its child really ran poisoned.)
+bool poison_alloc() {
+    static const bool on = [] {
+        const char *v = getenv("FFTCONV_POISON_ALLOC");
+        const bool p = v && atoi(v) > 0;
+        if (p) fputs("fftconv: FFTCONV_POISON_ALLOC on\n", stderr);
+        return p;
+    }();
+    return on;
+}
+// a raw hipMalloc'd table, before its upload (which must cover all of it)
+hipError_t poison_table(void *p, size_t bytes) {
+    if (!poison_alloc()) return hipSuccess;
+    const hipError_t e = hipMemset(p, 0xff, bytes);
+    return e != hipSuccess ? e : hipDeviceSynchronize();
+}
+
 template <class T>
 struct DevPtr {
     T *p = nullptr;
@@ -90,14 +113,7 @@ struct DevPtr {
             return fail(e == hipErrorOutOfMemory ? FFTCONV_E_NOMEM : FFTCONV_E_DEVICE,
                         std::string("hipMalloc: ") + hipGetErrorString(e));
         }
-        // (tests: FFTCONV_POISON_ALLOC=1 fills every new device buffer with NaN
-        // bytes, so a read of memory the path never wrote shows in the output
-        // instead of reading whatever the allocator recycled)
-        static const bool poison = [] {
-            const char *v = getenv("FFTCONV_POISON_ALLOC");
-            return v && atoi(v) > 0;
-        }();
-        if (poison) {  // (done before any stream uses the buffer: null stream, then wait)
+        if (poison_alloc()) {  // (done before any stream uses the buffer: null stream, then wait)
             if (hipMemset(p, 0xff, count * sizeof(T)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
                 return fail(FFTCONV_E_DEVICE, "poison memset");
         }
@@ -215,6 +231,7 @@ struct PinnedStage {
             return fail(FFTCONV_E_NOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
         }
         n = count;
+        if (poison_alloc()) std::memset(p, 0xff, count * sizeof(float));
         HIP_TRY(hipEventCreateWithFlags(&busy, hipEventDisableTiming));
         return FFTCONV_OK;
     }
@@ -3526,7 +3543,8 @@ int fft_twiddles(int dev, int log2n, hipStream_t s, const float2 **out) {
     }
     float2 *p = nullptr;
     HIP_TRY(hipMalloc((void **)&p, N * sizeof(float2)));
-    hipError_t e = hipMemcpyAsync(p, t.data(), N * sizeof(float2), hipMemcpyHostToDevice, s);
+    hipError_t e = poison_table(p, N * sizeof(float2));
+    if (e == hipSuccess) e = hipMemcpyAsync(p, t.data(), N * sizeof(float2), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);  // (t is freed on return)
     if (e != hipSuccess) {
         (void)hipFree(p);
@@ -3564,7 +3582,8 @@ int lg_tables(int dev, int log2m, LgTab *out) {
         fill(t.data() + M, A, A);
         fill(t.data() + M + A, Bt, Bt);
         HIP_TRY(hipMalloc((void **)&p, t.size() * sizeof(float2)));
-        hipError_t e = hipMemcpy(p, t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice);
+        hipError_t e = poison_table(p, t.size() * sizeof(float2));
+        if (e == hipSuccess) e = hipMemcpy(p, t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice);
         if (e != hipSuccess) {
             (void)hipFree(p);
             return fail(FFTCONV_E_DEVICE, std::string("twiddle upload: ") + hipGetErrorString(e));
@@ -3663,7 +3682,8 @@ int bluestein_tables(int dev, size_t n, int log2p, hipStream_t s, const float2 *
         }
         float2 *d = nullptr;
         HIP_TRY(hipMalloc((void **)&d, bytes));
-        hipError_t e = hipMemcpyAsync(d, t.data(), bytes, hipMemcpyHostToDevice, s);
+        hipError_t e = poison_table(d, bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(d, t.data(), bytes, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);  // (t is freed on return)
         if (e != hipSuccess) {
             (void)hipFree(d);
@@ -3710,6 +3730,7 @@ int fft_rows(int device, size_t n, size_t rows, const float *din, size_t is, flo
             if (int r = lg_tables(device, lp, &t)) return r;
             batch = std::max<size_t>(1, std::min(rows, ((size_t)64 << 20) / (P * sizeof(float2))));
             HIP_TRY(hipMallocAsync((void **)&scr, batch * P * sizeof(float2), s));
+            if (poison_alloc()) HIP_TRY(hipMemsetAsync(scr, 0xff, batch * P * sizeof(float2), s));
         } else {
             if (int r = fft_twiddles(device, lp + 1, s, &twP)) return r;  // W_{2P}
         }
@@ -3729,6 +3750,7 @@ int fft_rows(int device, size_t n, size_t rows, const float *din, size_t is, flo
         const size_t batch = std::max<size_t>(1, std::min(rows, ((size_t)64 << 20) / (m * sizeof(float2))));
         float2 *scr = nullptr;
         HIP_TRY(hipMallocAsync((void **)&scr, batch * m * sizeof(float2), s));
+        if (poison_alloc()) HIP_TRY(hipMemsetAsync(scr, 0xff, batch * m * sizeof(float2), s));
         const hipError_t e = launch_fft_large(log2m, inverse, a, t, scr, (int)rows, (int)batch, s);
         HIP_TRY(hipFreeAsync(scr, s));
         HIP_TRY(e);
