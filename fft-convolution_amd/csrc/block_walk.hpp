@@ -44,6 +44,13 @@ struct LookaheadClock {
     void begin_chunk(size_t fill, size_t cur, size_t act) {
         if (fill == 0 && (!windows || cur >= act)) tv = t + 1;
     }
+    // ahead of a chunk's launch of a convolver that idles (a crossfaded pair's
+    // convolver the crossfader has Reached away from): the block
+    // makes no anchor and reads no window, and whatever was anchored before the
+    // idle spell never counts again -- t moves on, tv stays ahead of it
+    void idle_chunk(size_t fill) {
+        if (fill == 0) tv = t + 1;
+    }
     void block_done() { ++t; }
     // reset() with `fill` samples buffered: the block in progress is dropped and
     // its number is not used again

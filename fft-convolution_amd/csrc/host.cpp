@@ -2250,6 +2250,14 @@ struct MatrixBase : BlockWalk {
         return matrix_process_host(self(), *this, in, in_len, out, out_len);
     }
 
+    // What a crossfaded pair (MatrixCrossfadeCoreT) asks of its two convolvers
+    // beyond the block walk; a matrix without windows has nothing to add.
+    bool xf_in_step(const D &) const { return true; }
+    void xf_swapped() {}
+    template <class XfArgs>
+    static void xf_chunk_begin(XfArgs &, D &, D &) {}
+    static void xf_block_done(D &, D &) {}
+
     // #[derive(Clone)] of the base's part; `owner`: the clone is a crossfade's
     // convolver -- it runs on that stream and stages updates through its owner.
     // (The caller waits for the stream.)
@@ -2372,7 +2380,9 @@ struct MatrixCore : MatrixBase<MatrixCore> {
 // the near / far partial sums and the block clock that schedules the anchors.
 // ---------------------------------------------------------------------------
 struct MatrixLookaheadCore {
+    static constexpr const char *kName = "lookahead matrix";
     static constexpr size_t Q = kMatrixLaQ;
+    using XfArgs = MatrixLaXfArgs;
     MatrixCore m;
     DevPtr<float2> far;  // [O][Pf_max][Q][B]; the near partial sums use m.part (Pn <= the dense P)
     LookaheadClock clk;
@@ -2452,8 +2462,40 @@ struct MatrixLookaheadCore {
         return matrix_process_host(*this, m, in, in_len, out, out_len);
     }
 
-    int clone_from(const MatrixLookaheadCore &o) {  // #[derive(Clone)]: the windows and the clock too
-        if (int r = m.clone_from(o.m)) return r;
+    // The fused crossfade launch (matrix_la_xf.hip) of the pair (a, b), `x.live`
+    // set: what it takes beyond the shared arguments, and the window rules of
+    // DESIGN §4t -- a live convolver's clock runs as in process_device, an idle
+    // one's windows are kept invalid, both count the block.
+    void xf_args(XfArgs &x) const {
+        x.P = near_parts();
+        x.rpp = (int)ceil_div(near_rows(), (size_t)x.P);
+        x.Pf = far_parts();
+        x.rppf = x.Pf ? (int)ceil_div(far_rows(), (size_t)x.Pf) : 0;
+    }
+    bool xf_in_step(const MatrixLookaheadCore &o) const { return clk.t == o.clk.t; }
+    void xf_swapped() { clk.invalidate(m.fill); }
+    static void xf_chunk_begin(XfArgs &x, MatrixLookaheadCore &a, MatrixLookaheadCore &b) {
+        MatrixLookaheadCore *cv[2] = {&a, &b};
+        for (int c = 0; c < 2; ++c) {
+            if ((x.live >> c) & 1)
+                cv[c]->clk.begin_chunk(cv[c]->m.fill, cv[c]->m.cur, cv[c]->m.act);
+            else
+                cv[c]->clk.idle_chunk(cv[c]->m.fill);
+            x.far[c] = cv[c]->far.p;
+            x.tv[c] = cv[c]->clk.tv;
+        }
+        x.t = a.clk.t;
+    }
+    static void xf_block_done(MatrixLookaheadCore &a, MatrixLookaheadCore &b) {
+        a.clk.block_done();
+        b.clk.block_done();
+    }
+    static hipError_t launch_xf_chunk(int log2b, const XfArgs &x, hipStream_t s) { return launch_matrix_la_xf_chunk(log2b, x, s); }
+
+    // #[derive(Clone)]: the windows and the clock too; `owner`: the clone is a
+    // crossfade's convolver on that stream
+    int clone_from(const MatrixLookaheadCore &o, hipStream_t owner = nullptr) {
+        if (int r = m.clone_from(o.m, owner)) return r;
         DeviceGuard g(m.device);
         clk = o.clk;
         if (int r = clone_buffer(far, o.far, m.stream)) return r;
@@ -2790,6 +2832,17 @@ struct SparseMatrixLookaheadCore {
     }
 };
 
+// where a handle's device, StreamOrder and stream (and a matrix's geometry,
+// buffers and state) live: the core itself, or a lookahead core's matrix
+template <class C>
+const C &base(const C &c) { return c; }
+template <class C>
+C &base(C &c) { return c; }
+inline const MatrixCore &base(const MatrixLookaheadCore &c) { return c.m; }
+inline MatrixCore &base(MatrixLookaheadCore &c) { return c.m; }
+inline const SparseMatrixCore &base(const SparseMatrixLookaheadCore &c) { return c.m; }
+inline SparseMatrixCore &base(SparseMatrixLookaheadCore &c) { return c.m; }
+
 // ---------------------------------------------------------------------------
 // MatrixCrossfadeCoreT -- P CrossfadeConvolver<FFTConvolver> instances in
 // lockstep, one per pair of a dense or a sparse (§4p) matrix: two
@@ -2810,7 +2863,10 @@ struct SparseMatrixLookaheadCore {
 // Conv supplies kName, check_list, rebuild_plan (a swap that changes the target
 // convolver's active_seg_count rebuilds what depends on it before that
 // convolver's next launch), and the fused launch: XfArgs, xf_args,
-// launch_xf_chunk.
+// launch_xf_chunk.  Conv's geometry, buffers and block walk are read through
+// base(conv): Conv itself, or the matrix a lookahead core wraps,
+// whose far-row windows follow the pair through the xf_* hooks -- xf_in_step,
+// xf_swapped, xf_chunk_begin, xf_block_done, no-ops for a matrix without windows.
 // ---------------------------------------------------------------------------
 template <class Conv>
 struct MatrixCrossfadeCoreT {
@@ -2854,8 +2910,11 @@ struct MatrixCrossfadeCoreT {
         }
     }
 
+    // (Conv's geometry, buffers and block walk are its base()'s: Conv itself, or
+    // the matrix a lookahead core wraps)
     bool states_agree() const {
-        return a->cur == b->cur && a->act == b->act && a->fill == b->fill && a->act > 0;
+        const auto &ma = base(*a), &mb = base(*b);
+        return ma.cur == mb.cur && ma.act == mb.act && ma.fill == mb.fill && ma.act > 0 && a->xf_in_step(*b);
     }
     // the convolver that is not the crossfader's target, and the target
     Conv &other_conv() const { return xf.target == 0 ? *b : *a; }
@@ -2883,16 +2942,16 @@ struct MatrixCrossfadeCoreT {
     // CrossfadeConvolver::new (:19-43)
     int init_new(const Conv &conv, size_t max_response_length, size_t mbs, size_t crossfade_samples) {
         if (mbs > (size_t)INT32_MAX) return fail(FFTCONV_E_UNSUPPORTED, "max_buffer_size exceeds 2^31-1");
-        device = conv.device;
-        I = conv.I;
-        O = conv.O;
-        P = conv.P;
+        device = base(conv).device;
+        I = base(conv).I;
+        O = base(conv).O;
+        P = base(conv).P;
         DeviceGuard g(device);
         if (int r = clone_convolvers(conv, conv)) return r;
         in_step = states_agree();
         stored_len = max_response_length;
         stored_stride = stored_len;
-        stage_row = std::max(stored_len, a->ir_len);
+        stage_row = std::max(stored_len, base(*a).ir_len);
         max_buffer_size = mbs;
         if (int r = alloc_buffers(P * stage_row)) return r;
         if (stored.n) HIP_TRY(hipMemsetAsync(stored.p, 0, stored.bytes(), stream));
@@ -2927,7 +2986,7 @@ struct MatrixCrossfadeCoreT {
     int swap_pairs_device(const uint32_t *lst, size_t n, const float *src, size_t stride, bool by_pair,
                           size_t len_data, size_t len_active, hipStream_t s) {
         const int to = xf.target == 0 ? 1 : 0;
-        Conv &t = other_conv(), &other = target_conv();
+        auto &t = base(other_conv()), &other = base(target_conv());
         if (len_active > t.ir_len) return fail(FFTCONV_E_INVALID, "New impulse response is longer than initialized length");
         if (int r = lists.acquire()) return r;
         if (n) std::copy(lst, lst + n, lists.tr());
@@ -2935,6 +2994,7 @@ struct MatrixCrossfadeCoreT {
         if (t.ir_len != 0) {
             const size_t act0 = t.act;
             if (int r = t.set_active(ceil_div(len_active, t.B), s)) return r;   // update's side effects (:186-190)
+            other_conv().xf_swapped();
             t.last_len = len_active;
             if (t.act != act0)
                 if (int r = t.rebuild_plan(s)) return r;
@@ -2983,13 +3043,13 @@ struct MatrixCrossfadeCoreT {
                      size_t len, size_t stride, hipStream_t s) {
         if (int r = check_poisoned()) return r;
         uint32_t *lst = lists.idx.data();
-        if (int r = a->check_list(n, pair_out, pair_in, lst)) return r;
-        Conv &t = other_conv(), &base = target_conv();
+        if (int r = base(*a).check_list(n, pair_out, pair_in, lst)) return r;
+        auto &t = base(other_conv()), &tgt = base(target_conv());
         const bool fading = is_crossfading();
         DeviceGuard g(device);
         if (!fading && !response_pending) {
             // the base set is the target convolver's, at the length it was applied at
-            const size_t lenp = base.last_len;
+            const size_t lenp = tgt.last_len;
             if (len > lenp)
                 return fail(FFTCONV_E_INVALID, "update_pairs: response longer than the length the response set was applied at");
             if (int r = order.enter(s)) return r;
@@ -3005,7 +3065,7 @@ struct MatrixCrossfadeCoreT {
             return fail(FFTCONV_E_INVALID, fading ? "assertion failed: response_len <= self.stored_response.len()"
                                                   : "update_pairs: response longer than the stored response");
         const bool whole = response_pending && !book.partial;
-        if (!whole && ceil_div(stored_len, base.B) != base.act)
+        if (!whole && ceil_div(stored_len, tgt.B) != tgt.act)
             return fail(FFTCONV_E_UNSUPPORTED, "update_pairs during a fade: the stored length gives another active segment "
                                                "count than the base convolver's, so zero-padding cannot reproduce update()");
         if (!fading && stored_len > t.ir_len)
@@ -3040,7 +3100,7 @@ struct MatrixCrossfadeCoreT {
         const bool shared = stride == 0 && P > 1;
         const size_t rows = shared ? 1 : P;
         if (!is_crossfading()) {
-            Conv &t = other_conv();
+            auto &t = base(other_conv());
             if (len > t.ir_len) return fail(FFTCONV_E_INVALID, "New impulse response is longer than initialized length");
             if (int r = order.enter(stream)) return r;
             if (len)
@@ -3104,10 +3164,13 @@ struct MatrixCrossfadeCoreT {
     // the path follows from the updated convolver's NEW active_seg_count
     int path_next() const {
         if (!is_crossfading() && response_pending) {
-            const Conv &t = other_conv(), &other = target_conv();
+            const auto &t = base(other_conv()), &other = base(target_conv());
             if (t.ir_len == 0 || stored_len > t.ir_len) return path_now();  // (the update changes nothing)
             const size_t act = ceil_div(stored_len, t.B);
-            return fused && in_step && act > 0 && act == other.act && t.cur == other.cur && t.fill == other.fill ? 1 : 0;
+            return fused && in_step && act > 0 && act == other.act && t.cur == other.cur && t.fill == other.fill &&
+                           a->xf_in_step(*b)
+                       ? 1
+                       : 0;
         }
         return path_now();
     }
@@ -3141,36 +3204,38 @@ struct MatrixCrossfadeCoreT {
         }
         if (mx.approaching) mx.vtab = mix_tab.p;  // the call's mix_value walk: launch A of the first chunk fills it
         typename Conv::XfArgs x{};
-        const Conv *cv[2] = {a.get(), b.get()};
+        auto &ma = base(*a), &mb = base(*b);
+        const decltype(&ma) cv[2] = {&ma, &mb};
         for (int c = 0; c < 2; ++c) {
             x.H[c] = cv[c]->H.p; x.X[c] = cv[c]->X.p; x.ovl[c] = cv[c]->ovl.p; x.ib[c] = cv[c]->ib.p;
             x.pre[c] = cv[c]->pre.p; x.part[c] = cv[c]->part.p;
         }
-        x.tw = a->tw.p;
+        x.tw = ma.tw.p;
         x.in_stride = (long long)is;
         x.out_stride = (long long)os;
-        x.I = (int)I; x.O = (int)O; x.S = (int)a->S;
-        x.act = (int)a->act;
-        x.nt_h = Variant::current().nt_matrix(a->H.bytes()) ? 1 : 0;
+        x.I = (int)I; x.O = (int)O; x.S = (int)ma.S;
+        x.act = (int)ma.act;
+        x.nt_h = Variant::current().nt_matrix(ma.H.bytes()) ? 1 : 0;
         x.live = xf.approaching ? 3 : (xf.target == 0 ? 1 : 2);
         x.mix = mx;
         a->xf_args(x);
         for (size_t done = 0; done < m;) {                              // FFTConvolver::process :222-294, A and B at once
-            const size_t k = a->chunk(m - done, a->B);
+            const size_t k = ma.chunk(m - done, ma.B);
             x.in = din + done;
             x.out = dout + done;
-            x.cur = (int)a->cur;
-            x.fill = (int)a->fill;
+            x.cur = (int)ma.cur;
+            x.fill = (int)ma.fill;
             x.k = (int)k;
             x.off = (int)done;
             x.walk = done == 0 && mx.approaching ? mix_tab.p : nullptr;
-            if (hipError_t e = Conv::launch_xf_chunk(a->log2b, x, s); e != hipSuccess) {
+            Conv::xf_chunk_begin(x, *a, *b);
+            if (hipError_t e = Conv::launch_xf_chunk(ma.log2b, x, s); e != hipSuccess) {
                 poisoned = true;
                 HIP_TRY(e);
             }
-            a->advance(k, a->B);
-            b->fill = a->fill;
-            b->cur = a->cur;
+            if (ma.advance(k, ma.B)) Conv::xf_block_done(*a, *b);
+            mb.fill = ma.fill;
+            mb.cur = ma.cur;
             done += k;
         }
         xf.advance(out_len);
@@ -3213,6 +3278,8 @@ struct MatrixCrossfadeCoreT {
 };
 using MatrixCrossfadeCore = MatrixCrossfadeCoreT<MatrixCore>;
 using SparseMatrixCrossfadeCore = MatrixCrossfadeCoreT<SparseMatrixCore>;
+// (A and B are lookahead matrices; the fused launch is matrix_la_xf.hip's)
+using MatrixLookaheadCrossfadeCore = MatrixCrossfadeCoreT<MatrixLookaheadCore>;
 
 
 // ---------------------------------------------------------------------------
@@ -3827,19 +3894,13 @@ struct fftconv_matrix_lookahead { MatrixLookaheadCore core; };
 struct fftconv_matrix_sparse_lookahead { SparseMatrixLookaheadCore core; };
 struct fftconv_matrix_crossfade { MatrixCrossfadeCore core; };
 struct fftconv_matrix_sparse_crossfade { SparseMatrixCrossfadeCore core; };
+struct fftconv_matrix_lookahead_crossfade { MatrixLookaheadCrossfadeCore core; };
 struct fftconv_matrix_twostage { MatrixTwoStageCore core; };
 struct fftconv_matrix_sparse_twostage { SparseMatrixTwoStageCore core; };
 
 // The wrappers the handle types repeat, over the handle struct H (the matrix
 // handles use all of them, the others those whose shape they share).
 namespace {
-
-// where a handle's device, StreamOrder and stream (and a matrix's geometry and
-// state) live: the core itself, or a lookahead core's matrix
-template <class C>
-const C &base(const C &c) { return c; }
-inline const MatrixCore &base(const MatrixLookaheadCore &c) { return c.m; }
-inline const SparseMatrixCore &base(const SparseMatrixLookaheadCore &c) { return c.m; }
 
 template <class H, class... A>
 H *abi_init(A... args) {
@@ -4555,6 +4616,106 @@ int fftconv_matrix_crossfade_set_fused(fftconv_matrix_crossfade *h, int on) {
     return FFTCONV_OK;
 }
 int fftconv_matrix_crossfade_path(const fftconv_matrix_crossfade *h) { return h ? h->core.path_next() : 0; }
+
+// ---- matrix crossfade with far-row windows -------------------------
+fftconv_matrix_lookahead_crossfade *fftconv_matrix_lookahead_crossfade_init(int device, size_t inputs, size_t outputs,
+                                                                            const float *responses, size_t response_len,
+                                                                            size_t response_stride, size_t max_block_size,
+                                                                            size_t max_response_length) {
+    set_error("");
+    if (inputs && outputs && max_response_length >= response_len &&
+        next_pow2(max_block_size) > ((size_t)1 << kMatrixLaMaxLog2B)) {
+        (void)fail(FFTCONV_E_UNSUPPORTED, "matrix lookahead crossfade block size " + std::to_string(next_pow2(max_block_size)) +
+                                              " outside 32..512 (use the MatrixCrossfadeConvolver)");
+        return nullptr;
+    }
+    fftconv_matrix_lookahead *conv = fftconv_matrix_lookahead_init(device, inputs, outputs, responses, response_len,
+                                                                   response_stride, max_block_size, max_response_length);
+    if (!conv) return nullptr;
+    // Convolution::init (src/crossfade_convolver.rs:46-49)
+    fftconv_matrix_lookahead_crossfade *h =
+        fftconv_matrix_lookahead_crossfade_new(conv, response_len, max_block_size, response_len);
+    fftconv_matrix_lookahead_destroy(conv);
+    return h;
+}
+fftconv_matrix_lookahead_crossfade *fftconv_matrix_lookahead_crossfade_new(const fftconv_matrix_lookahead *convolver,
+                                                                           size_t max_response_length,
+                                                                           size_t max_buffer_size,
+                                                                           size_t crossfade_samples) {
+    return abi_crossfade_new<fftconv_matrix_lookahead_crossfade>(convolver, max_response_length, max_buffer_size,
+                                                                 crossfade_samples);
+}
+int fftconv_matrix_lookahead_crossfade_update(fftconv_matrix_lookahead_crossfade *h, const float *responses,
+                                              size_t response_len, size_t response_stride) {
+    return abi_update(h, responses, response_len, response_stride);
+}
+int fftconv_matrix_lookahead_crossfade_update_device(fftconv_matrix_lookahead_crossfade *h, const float *d_responses,
+                                                     size_t response_len, size_t response_stride, void *hip_stream) {
+    return abi_update_device(h, d_responses, response_len, response_stride, hip_stream);
+}
+int fftconv_matrix_lookahead_crossfade_update_pairs(fftconv_matrix_lookahead_crossfade *h, size_t n_pairs,
+                                                    const uint32_t *pair_out, const uint32_t *pair_in,
+                                                    const float *responses, size_t response_len, size_t response_stride) {
+    return abi_update_pairs(h, n_pairs, pair_out, pair_in, responses, false, response_len, response_stride, nullptr);
+}
+int fftconv_matrix_lookahead_crossfade_update_pairs_device(fftconv_matrix_lookahead_crossfade *h, size_t n_pairs,
+                                                           const uint32_t *pair_out, const uint32_t *pair_in,
+                                                           const float *d_responses, size_t response_len,
+                                                           size_t response_stride, void *hip_stream) {
+    return abi_update_pairs(h, n_pairs, pair_out, pair_in, d_responses, true, response_len, response_stride, hip_stream);
+}
+size_t fftconv_matrix_lookahead_crossfade_diff_pairs(const fftconv_matrix_lookahead_crossfade *h) {
+    return h ? h->core.book.nd : 0;
+}
+int fftconv_matrix_lookahead_crossfade_last_patch(const fftconv_matrix_lookahead_crossfade *h, size_t out2[2]) {
+    return abi_last_patch(h, out2);
+}
+int fftconv_matrix_lookahead_crossfade_reset(fftconv_matrix_lookahead_crossfade *h) { return abi_crossfade_reset(h); }
+int fftconv_matrix_lookahead_crossfade_process(fftconv_matrix_lookahead_crossfade *h, const float *input, size_t input_len,
+                                               float *output, size_t output_len) {
+    return abi_process(h, input, input_len, output, output_len);
+}
+int fftconv_matrix_lookahead_crossfade_process_device(fftconv_matrix_lookahead_crossfade *h, const float *d_input,
+                                                      size_t in_stride, float *d_output, size_t out_stride,
+                                                      size_t output_len, void *hip_stream) {
+    return abi_process_device(h, d_input, in_stride, d_output, out_stride, output_len, hip_stream);
+}
+int fftconv_matrix_lookahead_crossfade_process_device_steps(fftconv_matrix_lookahead_crossfade *h, const float *d_input,
+                                                            size_t in_stride, size_t in_step, float *d_output,
+                                                            size_t out_stride, size_t out_step, size_t output_len,
+                                                            size_t steps, void *hip_stream) {
+    return abi_process_device_steps(h, d_input, in_stride, in_step, d_output, out_stride, out_step, output_len, steps,
+                                    hip_stream);
+}
+int fftconv_matrix_lookahead_crossfade_is_crossfading(const fftconv_matrix_lookahead_crossfade *h) {
+    return h && h->core.is_crossfading() ? 1 : 0;
+}
+fftconv_matrix_lookahead_crossfade *fftconv_matrix_lookahead_crossfade_clone(const fftconv_matrix_lookahead_crossfade *h) {
+    return abi_clone(h);
+}
+void fftconv_matrix_lookahead_crossfade_destroy(fftconv_matrix_lookahead_crossfade *h) { delete h; }
+int fftconv_matrix_lookahead_crossfade_synchronize(fftconv_matrix_lookahead_crossfade *h) { return abi_synchronize(h); }
+size_t fftconv_matrix_lookahead_crossfade_inputs(const fftconv_matrix_lookahead_crossfade *h) { return h ? h->core.I : 0; }
+size_t fftconv_matrix_lookahead_crossfade_outputs(const fftconv_matrix_lookahead_crossfade *h) { return h ? h->core.O : 0; }
+int fftconv_matrix_lookahead_crossfade_set_fused(fftconv_matrix_lookahead_crossfade *h, int on) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    h->core.fused = on != 0;
+    return FFTCONV_OK;
+}
+int fftconv_matrix_lookahead_crossfade_path(const fftconv_matrix_lookahead_crossfade *h) {
+    return h ? h->core.path_next() : 0;
+}
+int fftconv_matrix_lookahead_crossfade_set_windows(fftconv_matrix_lookahead_crossfade *h, int on) {
+    if (!h) return fail(FFTCONV_E_INVALID, "null handle");
+    h->core.a->clk.windows = h->core.b->clk.windows = on != 0;
+    return FFTCONV_OK;
+}
+int fftconv_matrix_lookahead_crossfade_anchors(const fftconv_matrix_lookahead_crossfade *h, int which) {
+    if (!h || which < 0 || which > 1) return 0;
+    // (an idle convolver -- the fused path with the crossfader Reached at the other one -- makes no anchor)
+    if (h->core.path_next() == 2 && which != h->core.xf.target) return 0;
+    return (which == 0 ? h->core.a : h->core.b)->anchors();
+}
 
 // ---- sparse matrix crossfade ---------------------------------------
 fftconv_matrix_sparse_crossfade *fftconv_matrix_sparse_crossfade_init(int device, size_t inputs, size_t outputs,

@@ -570,6 +570,42 @@ struct MatrixSpXfArgs {
 // the chunk's two launches (32 <= B <= 8192)
 hipError_t launch_matrix_sp_xf_chunk(int log2b, const MatrixSpXfArgs &a, hipStream_t s);
 
+// MatrixLookaheadCrossfadeConvolver (matrix_la_xf.hip): one chunk of
+// the two lookahead matrices A and B of a crossfaded handle while they are in
+// step (MatrixXfArgs' condition, and equal block counts t) -- MatrixXfArgs with
+// MatrixLaArgs' far-row windows, one set of windows and one tv per convolver.
+// [0] = A, [1] = B.
+struct MatrixLaXfArgs {
+    const float2 *H[2];    // [O][I][S][B] each
+    float2 *X[2];          // [I][S][B] each; the chunk's row is written to both
+    float *ovl[2];         // [O][B]
+    float *ib[2];          // [I][B]; both maintained
+    float2 *pre[2];        // [O][B]
+    float2 *part[2];       // [O][Pn][B] near partial sums
+    float2 *far[2];        // [O][Pf][Q][B] far partial sums, window row = block % Q
+    const float2 *tw;      // W_N^k, k < N = 2B
+    const float *in;       // chunk of input 0 (+ in_stride per input)
+    long long in_stride;
+    float *out;            // chunk of output 0 (+ out_stride per output)
+    long long out_stride;
+    int I, O, S;
+    int P, rpp;            // near parts and near rows per part, as MatrixLaArgs' m.P, m.rpp
+    int Pf, rppf;          // as MatrixLaArgs (both convolvers have the same active_seg_count)
+    int cur, act, fill, k;
+    int nt_h;              // nontemporal H streams (Variant::nt_matrix of one H)
+    int live, off;         // as MatrixXfArgs: an idle convolver makes no anchor and reads no window
+    long long t;           // the block this chunk belongs to, the same for both convolvers
+    long long tv[2];       // as MatrixLaArgs, per convolver (read for a live convolver only)
+    CrossfadeMixArgs mix;
+    float *walk;
+};
+// the far workgroups of launch A: per live convolver its far outputs x Pf
+__host__ __device__ inline long long matrix_la_xf_far_groups(const MatrixLaXfArgs &a, int c) {
+    return (a.live >> c) & 1 ? (long long)matrix_la_far_outputs(a.t, a.tv[c], a.O) * a.Pf : 0;
+}
+// the chunk's two launches (32 <= B <= 512)
+hipError_t launch_matrix_la_xf_chunk(int log2b, const MatrixLaXfArgs &a, hipStream_t s);
+
 // update_pairs (matrix_patch.hip): patch the spectra H of one matrix
 // for listed pairs (pair = o * I + i) in one launch -- the pairs of `tr` are
 // transformed from their response rows (the bits launch_ir_segments writes),

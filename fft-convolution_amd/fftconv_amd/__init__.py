@@ -223,6 +223,28 @@ SIGNATURES = {
     "fftconv_matrix_sparse_crossfade_pairs": (_sz, [_vp]),
     "fftconv_matrix_sparse_crossfade_set_fused": (_i, [_vp, _i]),
     "fftconv_matrix_sparse_crossfade_path": (_i, [_vp]),
+    "fftconv_matrix_lookahead_crossfade_init": (_vp, [_i, _sz, _sz, _fp, _sz, _sz, _sz, _sz]),
+    "fftconv_matrix_lookahead_crossfade_new": (_vp, [_vp, _sz, _sz, _sz]),
+    "fftconv_matrix_lookahead_crossfade_update": (_i, [_vp, _fp, _sz, _sz]),
+    "fftconv_matrix_lookahead_crossfade_update_device": (_i, [_vp, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_lookahead_crossfade_update_pairs": (_i, [_vp, _sz, _u32p, _u32p, _fp, _sz, _sz]),
+    "fftconv_matrix_lookahead_crossfade_update_pairs_device": (_i, [_vp, _sz, _u32p, _u32p, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_lookahead_crossfade_diff_pairs": (_sz, [_vp]),
+    "fftconv_matrix_lookahead_crossfade_last_patch": (_i, [_vp, C.POINTER(_sz)]),
+    "fftconv_matrix_lookahead_crossfade_reset": (_i, [_vp]),
+    "fftconv_matrix_lookahead_crossfade_process": (_i, [_vp, _fp, _sz, _fp, _sz]),
+    "fftconv_matrix_lookahead_crossfade_process_device": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _vp]),
+    "fftconv_matrix_lookahead_crossfade_process_device_steps": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _sz, _sz, _vp]),
+    "fftconv_matrix_lookahead_crossfade_is_crossfading": (_i, [_vp]),
+    "fftconv_matrix_lookahead_crossfade_clone": (_vp, [_vp]),
+    "fftconv_matrix_lookahead_crossfade_destroy": (None, [_vp]),
+    "fftconv_matrix_lookahead_crossfade_synchronize": (_i, [_vp]),
+    "fftconv_matrix_lookahead_crossfade_inputs": (_sz, [_vp]),
+    "fftconv_matrix_lookahead_crossfade_outputs": (_sz, [_vp]),
+    "fftconv_matrix_lookahead_crossfade_set_fused": (_i, [_vp, _i]),
+    "fftconv_matrix_lookahead_crossfade_path": (_i, [_vp]),
+    "fftconv_matrix_lookahead_crossfade_set_windows": (_i, [_vp, _i]),
+    "fftconv_matrix_lookahead_crossfade_anchors": (_i, [_vp, _i]),
     "fftconv_matrix_twostage_init": (_vp, [_i, _sz, _sz, _fp, _sz, _sz, _sz, _sz]),
     "fftconv_matrix_twostage_update": (_i, [_vp, _fp, _sz, _sz]),
     "fftconv_matrix_twostage_reset": (_i, [_vp]),
@@ -1005,6 +1027,47 @@ class SparseMatrixCrossfadeConvolver(_MatrixCrossfade, _MatrixBase):
         return cls(_handle(h), convolver.inputs, convolver.outputs, convolver._pair_list, max_buffer_size)
 
 
+class MatrixLookaheadCrossfadeConvolver(_MatrixWindows, _MatrixCrossfade, _MatrixBase):
+    """The MatrixCrossfadeConvolver over two MatrixLookaheadConvolvers (fftconv.h,
+    "MatrixLookaheadCrossfadeConvolver"): the same crossfaded switching and
+    update_pairs, each live convolver's far rows summed once every `period`
+    blocks.  Blocks 32..512."""
+
+    _prefix = "matrix_lookahead_crossfade"
+
+    def __init__(self, h, inputs: int, outputs: int, max_buffer_size: int):
+        super().__init__(h, inputs, outputs)
+        self.max_buffer_size = max_buffer_size
+
+    def _clone_args(self):
+        return self.inputs, self.outputs, self.max_buffer_size
+
+    def _all_pairs(self):
+        return [(o, i) for o in range(self.outputs) for i in range(self.inputs)]
+
+    def anchors(self, which: int) -> int:
+        """Outputs of convolver `which` (0 = A, 1 = B) that anchor when the next
+        block starts; 0 for an idle convolver."""
+        return int(self._fn("anchors")(self._h, which))
+
+    @classmethod
+    def init(cls, responses, max_block_size: int, max_response_length: int, device: int = 0):
+        """Convolution::init (:46-49) over responses[O][I][len], as MatrixCrossfadeConvolver.init."""
+        r = _dense_responses(responses)
+        O, I, n = r.shape
+        h = cls._cfn("init")(device, I, O, _p(r), n, n, max_block_size, max_response_length)
+        return cls(_handle(h), I, O, max_block_size)
+
+    @classmethod
+    def new(cls, convolver: MatrixLookaheadConvolver, max_response_length: int, max_buffer_size: int,
+            crossfade_samples: int):
+        """CrossfadeConvolver::new (:19-43); the MatrixLookaheadConvolver is cloned."""
+        if not isinstance(convolver, MatrixLookaheadConvolver):
+            raise TypeError("convolver must be a MatrixLookaheadConvolver")
+        h = cls._cfn("new")(convolver._h, max_response_length, max_buffer_size, crossfade_samples)
+        return cls(_handle(h), convolver.inputs, convolver.outputs, max_buffer_size)
+
+
 class MatrixTwoStageConvolver(_Base):
     """Two-stage partitioning for the matrix (fftconv.h,
     "MatrixTwoStageConvolver"): inputs x outputs TwoStageFFTConvolver instances
@@ -1136,7 +1199,8 @@ class SparseMatrixTwoStageConvolver(_Base):
 __all__ = [
     "Fft", "FFTConvolver", "TwoStageFFTConvolver", "CrossfadeConvolver", "MatrixConvolver",
     "MatrixLookaheadConvolver", "SparseMatrixConvolver", "SparseMatrixLookaheadConvolver",
-    "MatrixCrossfadeConvolver", "SparseMatrixCrossfadeConvolver", "MatrixTwoStageConvolver",
+    "MatrixCrossfadeConvolver", "SparseMatrixCrossfadeConvolver", "MatrixLookaheadCrossfadeConvolver",
+    "MatrixTwoStageConvolver",
     "SparseMatrixTwoStageConvolver", "ConvolutionPanic",
     "NotImplementedInReference", "DeviceError", "complex_size", "compute_tail_block_size", "device_count",
     "lib", "LIB_PATH", "SIGNATURES",

@@ -67,6 +67,7 @@ typedef struct fftconv_matrix_sparse_crossfade fftconv_matrix_sparse_crossfade; 
 typedef struct fftconv_matrix_lookahead fftconv_matrix_lookahead; /* the matrix with far-row windows (below) */
 typedef struct fftconv_matrix_sparse_lookahead fftconv_matrix_sparse_lookahead; /* the sparse matrix with far-row windows (below) */
 typedef struct fftconv_matrix_crossfade fftconv_matrix_crossfade; /* inputs x outputs CrossfadeConvolver<FFTConvolver> instances (below) */
+typedef struct fftconv_matrix_lookahead_crossfade fftconv_matrix_lookahead_crossfade; /* the crossfaded matrix over two lookahead matrices (below) */
 typedef struct fftconv_matrix_twostage fftconv_matrix_twostage;   /* inputs x outputs TwoStageFFTConvolver instances (below) */
 typedef struct fftconv_matrix_sparse_twostage fftconv_matrix_sparse_twostage; /* one TwoStageFFTConvolver per listed pair (below) */
 
@@ -897,6 +898,93 @@ size_t fftconv_matrix_sparse_crossfade_pairs(const fftconv_matrix_sparse_crossfa
 int fftconv_matrix_sparse_crossfade_set_fused(fftconv_matrix_sparse_crossfade *h, int on);
 /* the path (0, 1 or 2) the next process() would take, a pending response included */
 int fftconv_matrix_sparse_crossfade_path(const fftconv_matrix_sparse_crossfade *h);
+
+/* ---- MatrixLookaheadCrossfadeConvolver: the crossfaded matrix with far-row windows ----
+ * fftconv_matrix_crossfade's definition, unchanged: I*O reference
+ * CrossfadeConvolver<FFTConvolver> instances in lockstep, one Crossfader, one
+ * pending response, the mix applied to the per-output sums, reset =
+ * FFTCONV_E_UNIMPLEMENTED, and the matrix's two departures.  The only
+ * difference: the two convolvers A and B are lookahead matrices
+ * (fftconv_matrix_lookahead), so each convolver's order of summation is that
+ * handle's -- pre = near + far, the same Pn / Pf rules, contiguous far row
+ * groups, ascending adds -- and a live convolver's far rows are summed once every
+ * fftconv_matrix_lookahead_period() blocks.  Blocks 32..512; a larger block is
+ * FFTCONV_E_UNSUPPORTED (use fftconv_matrix_crossfade).
+ * Every entry point mirrors fftconv_matrix_crossfade_* word for word, update_pairs
+ * and its errors included; `new` clones a fftconv_matrix_lookahead handle, its
+ * windows and its block count too.
+ * Windows, all host bookkeeping: (1) any swap into the convolver that is not the
+ * crossfader's target -- update, update_pairs, or the pending response applied by
+ * process() -- invalidates that convolver's windows, as
+ * fftconv_matrix_lookahead_update does; it sums its far rows in full until its
+ * outputs have anchored again, at most period - 1 blocks each.  (2) On the fused
+ * paths a convolver the crossfader has Reached away from is idle: it keeps its
+ * delay line, input buffer and block count, makes no anchor and reads no window,
+ * and its windows stay invalid for as long as it idles.  So no block ever reads a
+ * window row that was anchored before the last swap into its convolver or across
+ * an idle spell, and the bits do not depend on whether a far sum came from a
+ * window.
+ * Paths (fftconv_matrix_lookahead_crossfade_path): 0 composition (A and B as two
+ * lookahead matrices, then the mix kernel), 1 fused with both convolvers live, 2
+ * fused with one idle; "in step" is fftconv_matrix_crossfade's rule and equal
+ * block counts.  Every path computes the same bits, so: a fused call equals the
+ * composition call; windows on equals fftconv_matrix_lookahead_crossfade_set_windows(h, 0);
+ * a handle that was never updated equals a fftconv_matrix_lookahead over the
+ * same calls; once a fade has ended every sample equals a fftconv_matrix_lookahead
+ * that received the same update at the same call boundary; a matrix split by
+ * outputs gives identical rows; process_device_steps equals the separate calls. */
+fftconv_matrix_lookahead_crossfade *fftconv_matrix_lookahead_crossfade_init(int device, size_t inputs, size_t outputs,
+                                                                            const float *responses, size_t response_len,
+                                                                            size_t response_stride, size_t max_block_size,
+                                                                            size_t max_response_length);
+/* `convolver` is cloned (the caller keeps ownership of its handle). */
+fftconv_matrix_lookahead_crossfade *fftconv_matrix_lookahead_crossfade_new(const fftconv_matrix_lookahead *convolver,
+                                                                           size_t max_response_length,
+                                                                           size_t max_buffer_size,
+                                                                           size_t crossfade_samples);
+int fftconv_matrix_lookahead_crossfade_update(fftconv_matrix_lookahead_crossfade *h, const float *responses,
+                                              size_t response_len, size_t response_stride);
+int fftconv_matrix_lookahead_crossfade_update_device(fftconv_matrix_lookahead_crossfade *h, const float *d_responses,
+                                                     size_t response_len, size_t response_stride, void *hip_stream);
+int fftconv_matrix_lookahead_crossfade_update_pairs(fftconv_matrix_lookahead_crossfade *h, size_t n_pairs,
+                                                    const uint32_t *pair_out, const uint32_t *pair_in,
+                                                    const float *responses, size_t response_len, size_t response_stride);
+int fftconv_matrix_lookahead_crossfade_update_pairs_device(fftconv_matrix_lookahead_crossfade *h, size_t n_pairs,
+                                                           const uint32_t *pair_out, const uint32_t *pair_in,
+                                                           const float *d_responses, size_t response_len,
+                                                           size_t response_stride, void *hip_stream);
+/* |D|, as fftconv_matrix_crossfade_diff_pairs */
+size_t fftconv_matrix_lookahead_crossfade_diff_pairs(const fftconv_matrix_lookahead_crossfade *h);
+/* the last applied swap: out2 = {pairs transformed, pairs copied}; a whole update gives {I*O, 0} */
+int fftconv_matrix_lookahead_crossfade_last_patch(const fftconv_matrix_lookahead_crossfade *h, size_t out2[2]);
+int fftconv_matrix_lookahead_crossfade_reset(fftconv_matrix_lookahead_crossfade *h);
+/* input [inputs][input_len], output [outputs][output_len], host memory. */
+int fftconv_matrix_lookahead_crossfade_process(fftconv_matrix_lookahead_crossfade *h, const float *input, size_t input_len,
+                                               float *output, size_t output_len);
+/* device memory, stream-ordered, as fftconv_matrix_crossfade_process_device */
+int fftconv_matrix_lookahead_crossfade_process_device(fftconv_matrix_lookahead_crossfade *h, const float *d_input,
+                                                      size_t in_stride, float *d_output, size_t out_stride,
+                                                      size_t output_len, void *hip_stream);
+/* `steps` consecutive process_device calls; the same bits as the separate calls. */
+int fftconv_matrix_lookahead_crossfade_process_device_steps(fftconv_matrix_lookahead_crossfade *h, const float *d_input,
+                                                            size_t in_stride, size_t in_step, float *d_output,
+                                                            size_t out_stride, size_t out_step, size_t output_len,
+                                                            size_t steps, void *hip_stream);
+int fftconv_matrix_lookahead_crossfade_is_crossfading(const fftconv_matrix_lookahead_crossfade *h); /* 1/0 */
+fftconv_matrix_lookahead_crossfade *fftconv_matrix_lookahead_crossfade_clone(const fftconv_matrix_lookahead_crossfade *h);
+void fftconv_matrix_lookahead_crossfade_destroy(fftconv_matrix_lookahead_crossfade *h);
+int fftconv_matrix_lookahead_crossfade_synchronize(fftconv_matrix_lookahead_crossfade *h);
+size_t fftconv_matrix_lookahead_crossfade_inputs(const fftconv_matrix_lookahead_crossfade *h);
+size_t fftconv_matrix_lookahead_crossfade_outputs(const fftconv_matrix_lookahead_crossfade *h);
+/* on = 0: every call of this handle takes the composition path (default 1) */
+int fftconv_matrix_lookahead_crossfade_set_fused(fftconv_matrix_lookahead_crossfade *h, int on);
+/* the path (0, 1 or 2) the next process() would take, a pending response included */
+int fftconv_matrix_lookahead_crossfade_path(const fftconv_matrix_lookahead_crossfade *h);
+/* on = 0: both convolvers sum their far rows in full on every block (default 1; the same bits) */
+int fftconv_matrix_lookahead_crossfade_set_windows(fftconv_matrix_lookahead_crossfade *h, int on);
+/* the outputs of convolver `which` (0 = A, 1 = B) that anchor when the next
+ * block starts; 0 for an idle convolver */
+int fftconv_matrix_lookahead_crossfade_anchors(const fftconv_matrix_lookahead_crossfade *h, int which);
 
 /* ---- MatrixTwoStageConvolver: two-stage partitioning for the matrix ----
  * A matrix two-stage convolver (inputs I, outputs O, head block max_block_size,
